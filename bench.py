@@ -10,11 +10,15 @@ BASELINE.json: KPCN(n_in=39) + 2 x PathNet(36->3) + FeatureMSE (w=0.1, m11r11, t
 of 128x128 with S=8 spp per GPU, inputs resident in HBM, fused clip+Adam, RCCL gradient all-reduce when
 N > 1 (weak scaling: 8 patches per GPU).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, ...).
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``).
+``--full`` adds everything else the benchmark measures or checks, after the timed steps:
   roofline           dominant kernel class (conv implicit-GEMM, MFMA-bound): algorithmic FLOP / launch time
-                     measured with HIP events on the launch stream inside the timed region
+                     measured with HIP events on the launch stream in eagerly launched, profiled steps
   roofline_kernel_apply   the HBM-bound op the north star puts a >= 40 % target on
-  cpu_baseline       the CPU oracle's train step on this box's host cores (rank 0, N == 1 only)
+  measured_peaks, value_long, c2, other_precisions, other_parametrisation, multi_rank_path (N == 1),
+  allreduce and params_identical_across_ranks (N > 1)
+  cpu_baseline       the CPU oracle's train step on this box's host cores (rank 0, N == 1 only; --no-cpu-baseline: skipped)
 """
 import argparse
 import json
@@ -391,6 +395,25 @@ def cpu_baseline():
                    "branches), 64x64, batch 2, 3 train steps after one warm-up, %.2f s per step" % c1_t}}
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, itf):
+    """``--dump-outputs``: what the last timed step hands its caller -- the losses it logged (``loss.<key>``), the denoised
+    patches (``out.<radiance|diffuse|specular>``) and every model's updated parameters (``param.<model>.<name>``) -- whole,
+    as float32 ``out_dir/<name>.npy`` (49 MB at the benchmarked configuration)."""
+    import numpy as np
+    arrays = {"loss." + k: v for k, v in itf.last_loss_dict.items()}
+    arrays.update(("out." + k, v) for k, v in itf.last_out.items())
+    arrays.update(("param.%s.%s" % (m, k), p) for m, mod in itf.models.items() for k, p in mod.named_parameters())
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes, more than %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def self_launch(n, argv):
     """``python bench.py --gpus N`` without a launcher: start N fresh worker processes (one per GPU) through
     ``torch.distributed.run`` BEFORE this process makes any GPU call, pass rank 0's JSON line through, and exit with
@@ -437,7 +460,15 @@ def main():
     ap.add_argument("--precision", choices=("bf16x321h", "bf16x321o", "bf16x321", "bf16x3", "fp32"), default=None,
                     help="conv GEMM arithmetic: split-bf16 with 3 / 2 / 1 MFMAs per product in forward / data gradient / weight "
                          "gradient (default), 3 everywhere (rounds 1-2), or exact fp32 MFMA (roofline vs the 157.3 TF/s peak)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else (see the module doc-string): roofline "
+                         "figures, measured peaks, a longer segment, the C2 step, the other arithmetics and parametrisation, the "
+                         "multi-rank path, the all-reduce and replica checks (N > 1), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, denoised patches, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, sys.argv[1:])
 
@@ -500,7 +531,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    if args.eager:
+    if args.eager and args.full:
         ops.USE_SIDE_STREAM = False        # per-launch events need one stream
         ops.USE_BRANCH_STREAM = False
         ops.set_profiler(prof)
@@ -518,17 +549,20 @@ def main():
     my_elapsed = time.perf_counter() - t0
     elapsed = wd.max_over_ranks(my_elapsed, device)
     rank_ms = wd.gather_floats(my_elapsed / args.steps * 1e3, device)        # every rank's own ms per step (rank 0 reports min / max)
-    comm = wd.time_allreduce(itf.fused_optim, group, device) if world > 1 else None
-    # every rank's parameters after the timed steps, as an exact integer checksum (sum of the fp32 bit patterns): data-parallel
-    # replicas that saw the same summed gradients must hold the same bits
-    with torch.no_grad():
-        digest = sum(int(p.detach().contiguous().view(torch.int32).to(torch.int64).sum().item())
-                     for m in itf.models.values() for p in m.parameters())
-    digests = wd.gather_ints(digest, device)
     last_losses = {k: float(v) for k, v in itf.last_loss_dict.items()}       # of step warmup + steps, this rank
     ops.set_profiler(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, itf)          # (before --full's eager steps move the parameters on)
+    if args.full:
+        comm = wd.time_allreduce(itf.fused_optim, group, device) if world > 1 else None
+        # every rank's parameters after the timed steps, as an exact integer checksum (sum of the fp32 bit patterns): data-parallel
+        # replicas that saw the same summed gradients must hold the same bits
+        with torch.no_grad():
+            digest = sum(int(p.detach().contiguous().view(torch.int32).to(torch.int64).sum().item())
+                         for m in itf.models.values() for p in m.parameters())
+        digests = wd.gather_ints(digest, device)
     prof_elapsed = elapsed
-    if not args.eager:
+    if args.full and not args.eager:
         # The timed region above replays one hipGraph per step (no per-kernel events inside a graph).
         # Per-kernel durations for the roofline come from the same step launched eagerly right after,
         # HIP events on the launch stream around every conv / kernel-apply launch (same kernels, same shapes).
@@ -621,17 +655,18 @@ def main():
         # collect several kernels and are reported under roofline_other_conv (exact-fp32 mode: one kernel per class anyway)
         single = ([k for k in conv_keys if k not in ("conv_igemm", "conv_wgrad")] or conv_keys) if ops.split_path() else conv_keys
         dominant = max(single, key=lambda k: summ[k]["ms"]) if conv_keys else None
-        ka = kernel_apply_probe(device)
-        traffic = pmc_traffic()
-        for nm in ("fwd", "bwd"):
-            ka[nm]["traffic"] = traffic.get("kernel_apply_" + nm)
-            d = summ.get("kernel_apply_" + nm)          # the same kernel inside the (eagerly launched, profiled) train step
-            if d and d["ms"] > 0:
-                gbs = d["work"] / (d["ms"] * 1e-3) / 1e9
-                ka[nm]["in_step"] = {"achieved": round(gbs, 1), "frac": round(gbs / PEAK_HBM_GBS, 4), "launches": d["launches"],
-                                     "avg_launch_ms": round(d["ms"] / d["launches"], 4),
-                                     "note": "HIP events around the launches of the profiled eager steps; its algorithmic bytes "
-                                             "count logits + radiance + result (+ gradient) as SURVEY 8d does"}
+        if args.full:
+            ka = kernel_apply_probe(device)
+            traffic = pmc_traffic()
+            for nm in ("fwd", "bwd"):
+                ka[nm]["traffic"] = traffic.get("kernel_apply_" + nm)
+                d = summ.get("kernel_apply_" + nm)          # the same kernel inside the (eagerly launched, profiled) train step
+                if d and d["ms"] > 0:
+                    gbs = d["work"] / (d["ms"] * 1e-3) / 1e9
+                    ka[nm]["in_step"] = {"achieved": round(gbs, 1), "frac": round(gbs / PEAK_HBM_GBS, 4), "launches": d["launches"],
+                                         "avg_launch_ms": round(d["ms"] / d["launches"], 4),
+                                         "note": "HIP events around the launches of the profiled eager steps; its algorithmic bytes "
+                                                 "count logits + radiance + result (+ gradient) as SURVEY 8d does"}
         line = {
             "metric": "128x128 MC patches/sec (train step), KPCN-Manifold",
             "value": round(value, 3), "unit": "patches/s", "n_gpus": world, "steps": args.steps,
@@ -644,7 +679,6 @@ def main():
                            else 1 if world == 1 and args.backend == "nccl" else 0),
             "collective_backend": ("rccl" if args.backend == "nccl" else args.backend + (" (smoke test, shared GPU)" if args.share_gpu else "")),
             "rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
-            "params_identical_across_ranks": (len(set(digests)) == 1) if world > 1 else None,
             # capture validation (wcmc_amd.graph.capture_validated), this rank: ms per replay of every capture that was made; the last one is the step that ran
             "capture_attempts": None if args.eager else graphed.capture_attempts,
             "capture_ms": None if args.eager else graphed.capture_ms,
@@ -652,7 +686,6 @@ def main():
             # the two streams the halves replay on: picked once per process by a spin-kernel probe so that they sit on different
             # hardware queues (wcmc_amd.ops.concurrent_stream_pair)
             "stream_pair": (getattr(graphed.half_streams[0], "probe", None) if (not args.eager and graphed.two_stream) else None),
-            "allreduce": comm,
             # loss_dict of the last timed step on rank 0 (seeded weights, inputs and pairings: reproducible run to run
             # with the same binary; a stream-ordering race in the captured step would show here)
             "losses_last_step": {k: round(v, 6) for k, v in last_losses.items()},
@@ -696,29 +729,34 @@ def main():
                            "achieved_tflops": round(549.6e9 * global_batch * args.steps / elapsed / 1e12 / world, 1),
                            "frac_of_mfma_peak": round(549.6e9 * global_batch * args.steps / elapsed / 1e12 / world /
                                                       (PEAK_BF16_MFMA_TFLOPS if ops.split_path() else PEAK_FP32_MFMA_TFLOPS), 4)},
-            "roofline": dict(roof(dominant, "mfma"), traffic=traffic.get(dominant)) if dominant else None,
-            "roofline_other_conv": [dict(roof(k, "mfma"), traffic=traffic.get(k)) for k in conv_keys if k != dominant],
-            # families: every instance of one kernel template (and, for the U-Net, what is left of it in the catch-all class) summed --
-            # algorithmic FLOPs of all their launches / their HIP-event time -- so that the figure does not depend on how the template
-            # arguments split the time
-            "roofline_family": [f for f in (family("conv_halo64 (KPCN 5x5 forward + data gradient, every instance)",
-                                                   [k for k in conv_keys if k.startswith("conv_halo64")]),
-                                            family("U-Net 3x3 forward + data gradient (conv_halo3 instances + class conv_igemm)",
-                                                   [k for k in conv_keys if k.startswith("conv_halo3") or k == "conv_igemm"]),
-                                            family("weight gradients (conv_wgrad_rows + class conv_wgrad)",
-                                                   [k for k in conv_keys if k.startswith("conv_wgrad")])) if f],
-            "roofline_pointwise": (dict(roof("conv_pw", "hbm"), traffic=traffic.get("conv_pw")) if roof("conv_pw", "hbm") else None),
-            # PathNet.embedding / PathNet.final as one launch per direction (hidden activations never leave the CU): HBM-bound by
-            # construction, algorithmic bytes = input + output (+ gradients) once
-            "roofline_pathnet_fused": [dict(roof(k, "hbm"), traffic=traffic.get(k))
-                                       for k in ("embed3_fwd", "embed3_bwd", "final2_fwd", "final2_bwd") if roof(k, "hbm")],
-            "roofline_kernel_apply": ka,
         }
-        line["measured_peaks"] = measured_peaks(device)
+        if args.full:
+            line.update({
+                "params_identical_across_ranks": (len(set(digests)) == 1) if world > 1 else None,
+                "allreduce": comm,
+                "roofline": dict(roof(dominant, "mfma"), traffic=traffic.get(dominant)) if dominant else None,
+                "roofline_other_conv": [dict(roof(k, "mfma"), traffic=traffic.get(k)) for k in conv_keys if k != dominant],
+                # families: every instance of one kernel template (and, for the U-Net, what is left of it in the catch-all class) summed --
+                # algorithmic FLOPs of all their launches / their HIP-event time -- so that the figure does not depend on how the template
+                # arguments split the time
+                "roofline_family": [f for f in (family("conv_halo64 (KPCN 5x5 forward + data gradient, every instance)",
+                                                       [k for k in conv_keys if k.startswith("conv_halo64")]),
+                                                family("U-Net 3x3 forward + data gradient (conv_halo3 instances + class conv_igemm)",
+                                                       [k for k in conv_keys if k.startswith("conv_halo3") or k == "conv_igemm"]),
+                                                family("weight gradients (conv_wgrad_rows + class conv_wgrad)",
+                                                       [k for k in conv_keys if k.startswith("conv_wgrad")])) if f],
+                "roofline_pointwise": (dict(roof("conv_pw", "hbm"), traffic=traffic.get("conv_pw")) if roof("conv_pw", "hbm") else None),
+                # PathNet.embedding / PathNet.final as one launch per direction (hidden activations never leave the CU): HBM-bound by
+                # construction, algorithmic bytes = input + output (+ gradients) once
+                "roofline_pathnet_fused": [dict(roof(k, "hbm"), traffic=traffic.get(k))
+                                           for k in ("embed3_fwd", "embed3_bwd", "final2_fwd", "final2_bwd") if roof(k, "hbm")],
+                "roofline_kernel_apply": ka,
+            })
+            line["measured_peaks"] = measured_peaks(device)
         # the practical matrix peak of THIS box: what a dense 8192^3 bf16 hipBLASLt GEMM sustains (clock under MFMA load, not the 2.5 PF
         # of the data sheet); `issued_vs_measured_gemm` = MFMA FLOPs a conv kernel issues per second (terms per product, padding not
         # counted) / that rate -- how far the kernel is from what the matrix pipe delivers here, where `frac` is against the spec peak
-        gemm = line["measured_peaks"].get("bf16_gemm_8192_TFLOPs")
+        gemm = line["measured_peaks"].get("bf16_gemm_8192_TFLOPs") if args.full else None
         if gemm and ops.split_path() and ops.reduced_backward() and prof.step:
             # MFMA FLOPs ONE step issues: the conv classes' algorithmic FLOPs x MFMAs per product (HIP-event classes of the profiled
             # steps), + the fused 1x1 PathNet chains by their shapes (forward 3, data gradient 2, weight gradient 1 MFMAs per product;
@@ -735,7 +773,7 @@ def main():
             for obj in [line["roofline"]] + line["roofline_other_conv"] + line["roofline_family"]:
                 if obj and obj.get("issued_mfma_TFLOPs"):
                     obj["issued_vs_measured_gemm"] = round(obj["issued_mfma_TFLOPs"] / gemm, 3)
-        if world == 1 and not args.eager:
+        if args.full and world == 1 and not args.eager:
             ops.USE_SIDE_STREAM, ops.USE_BRANCH_STREAM = stream_defaults
             itf.fused_optim.leave_grads = False            # (back to the captured buffers: the long segment replays the graph)
             # a longer segment of the SAME graphed step right behind the official one (the driver's 20 steps are 0.27 s of a 20 s
@@ -789,9 +827,11 @@ def main():
                     torch.distributed.destroy_process_group()
                 except Exception as err:                       # (reported, never fatal for the headline)
                     line["multi_rank_path"] = {"error": repr(err)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
+    if world == 1 and not args.eager and not args.full:
+        graphed.close()                    # (--full closes it after its longer segment: the run ends without a live capture)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -18,7 +18,7 @@ bash scripts/ab_trees.sh _r05 . 3
 fi
 } > $O/r06_step_ab.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/trace_full -- python3 $R/bench.py --steps 16 --warmup 3 --no-cpu-baseline > $O/trace_full.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/trace_full -- python3 $R/bench.py --full --steps 16 --warmup 3 --no-cpu-baseline > $O/trace_full.log 2>&1
 cd $R
 python3 scripts/trace_gaps.py $O/trace_full > $O/r06_step_kernels.txt 2>&1
 rm -rf $O/trace_full

@@ -17,21 +17,21 @@ done
 cd $R
 python3 scripts/pmc_summary.py $O/pmc > $O/pmc_summary.json
 cp $O/pmc_summary.json $R/profiles/${TAG}_pmc_summary.json
-python3 $R/bench.py --steps 30 --warmup 5 > $O/bench_line.log 2>&1
+python3 $R/bench.py --full --steps 30 --warmup 5 > $O/bench_line.log 2>&1
 tail -1 $O/bench_line.log | cut -c1-200
-python3 $R/bench.py --steps 20 --warmup 5 --precision bf16x3 --no-cpu-baseline > $O/bench_line_bf16x3.log 2>&1
+python3 $R/bench.py --full --steps 20 --warmup 5 --precision bf16x3 --no-cpu-baseline > $O/bench_line_bf16x3.log 2>&1
 tail -1 $O/bench_line_bf16x3.log | cut -c1-200
-python3 $R/bench.py --steps 10 --warmup 3 --precision fp32 --no-cpu-baseline > $O/bench_line_fp32.log 2>&1
+python3 $R/bench.py --full --steps 10 --warmup 3 --precision fp32 --no-cpu-baseline > $O/bench_line_fp32.log 2>&1
 tail -1 $O/bench_line_fp32.log | cut -c1-200
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_graph -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_eager -- python3 $R/bench.py --eager --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_eager_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_graph -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_eager -- python3 $R/bench.py --full --eager --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_eager_under_rocprof.log 2>&1
 cd $R
 python3 scripts/trace_gaps.py $O/prof_graph > $O/step_trace_gaps.txt 2>&1
 python3 -m pytest tests/test_gpu_bench_config.py -q -m gpu > $O/bench_config_test.log 2>&1; tail -1 $O/bench_config_test.log
 cat gpurun_out/bench_config_parity_device_seed0.txt gpurun_out/bench_config_parity_device_seed1.txt gpurun_out/bench_config_parity_device_seed2.txt > $O/bench_config_parity_device.txt
 set +x
-for i in 1 2 3; do python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['dtype'], d['roofline']['class'], d['roofline']['frac'], 'long', d['value_long']['value'], 'c2', d['c2']['value'], {k: v['value'] for k, v in d['other_precisions'].items()}, 'multi_rank_path', d['multi_rank_path']['value'], d['multi_rank_path']['tail_ms'], 'overlap_allreduce', d['multi_rank_path']['overlap_allreduce']['value'])"; done > $O/bench_runs.txt 2>&1
+for i in 1 2 3; do python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['dtype'], d['roofline']['class'], d['roofline']['frac'], 'long', d['value_long']['value'], 'c2', d['c2']['value'], {k: v['value'] for k, v in d['other_precisions'].items()}, 'multi_rank_path', d['multi_rank_path']['value'], d['multi_rank_path']['tail_ms'], 'overlap_allreduce', d['multi_rank_path']['overlap_allreduce']['value'])"; done > $O/bench_runs.txt 2>&1
 set -x
 find $O/prof_graph $O/prof_eager -name "*kernel_stats.csv" | head
 # keep the merge under the 64 MiB limit: only the stats / counter CSVs go home

@@ -1,5 +1,5 @@
 """Idle time and overlap inside the graphed step, from a rocprofv3 kernel trace:
-   rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline
+   rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline
    python3 scripts/trace_gaps.py OUT
 Takes the last replays of the captured step (recognised by their period), prints per step: wall time, union of the kernel
 intervals (= time with at least one kernel running), the idle gaps, and the time with two or more kernels in flight."""

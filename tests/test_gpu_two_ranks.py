@@ -24,7 +24,7 @@ def test_two_ranks_run_the_graphed_split_tail_step_on_one_gpu():
     env = dict(os.environ)
     env.pop("WCMC_DEBUG_LIB", None)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "3",
            "--warmup", "1", "--no-cpu-baseline"]
     proc = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, "bench.py --gpus 2 failed:\n%s\n%s" % (proc.stdout[-3000:], proc.stderr[-3000:])
