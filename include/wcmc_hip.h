@@ -539,6 +539,35 @@ int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float
                                float* specular_buffer, float* albedo, float* paths, float* target_diffuse,
                                float* target_specular, float* target_total, void* stream);
 
+/* ---------------------------------------------------------------- full-frame evaluation
+ * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
+ * (scene, spp) cell.  out / ipt / tgt: fp32 (H, W, 3) images, element (y, x, c) at p[y*sh + x*sw + c*sc] (any int64
+ * strides: the channel-first frame is passed as a view); has_hit: the same form, or null.  When given, out is replaced
+ * by ipt wherever has_hit == 0 (test_models.py:231-232) on load.
+ * result: 40 fp64 device values [cmp][t][k] -- cmp 0 = out vs tgt, 1 = ipt vs tgt; tone map t in (linear, _tonemap,
+ * tonemap gamma 1/2.2, tonemap gamma 1/2.8), each image on its own luminance; metric k in (RelMSE, RelL1, DSSIM, L1, MSE):
+ *   MSE = mean (a-r)^2, L1 = mean |a-r|, RelL1 = mean |a-r| / (|r| + eps),
+ *   RelMSE = mean over the non-NaN entries of (a-r)^2 / (r^2 + eps) (NaN when all are NaN),
+ *   DSSIM = 1 - SSIM: 7x7 uniform window, K1 0.01, K2 0.03, sample covariance (49/48), data_range 2, fp64, the SSIM map
+ *   averaged over the interior cropped by 3 pixels and over the channels (skimage.metrics.structural_similarity with
+ *   multichannel=True before 0.21, as specified in DESIGN.md).
+ * H, W >= 7.  Two launches (blocks' partial sums, then a one-block finish in a fixed order): bitwise reproducible. */
+size_t wcmc_image_eval_workspace_bytes(int H, int W);
+int wcmc_image_eval(const float* out, int64_t osh, int64_t osw, int64_t osc, const float* ipt, int64_t ish, int64_t isw,
+                    int64_t isc, const float* tgt, int64_t tsh, int64_t tsw, int64_t tsc, const float* has_hit, int64_t hsh,
+                    int64_t hsw, int64_t hsc, int H, int W, double eps, double* result, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The tile loop of test_models.inference (test_models.py:75-89) for one batch of B tiles: for every tile b with
+ * coords[b] = (i_start, j_start, i_end, j_end, i, j) (device int32 (B, 6)), copy its owned window
+ * [i_start:i_end, j_start:j_end] of
+ *   the radiance: rad (B, 3, ho, wo) with strides (rsb, rsc, rsh, rsw), 'replicate'-padded back to P x P
+ *     (F.pad(out, (pw//2, pw-pw//2, ph//2, ph-ph//2)), test_models.py:66-70) -> out_rad (3, H, W) contiguous;
+ *   up to two P-buffers: pbuf (B, S, C, P, P) contiguous -> out_pbuf (S, C, H, W) contiguous (null: none).
+ * ho == wo == P (no padding) or both smaller than P.  Windows outside the frame or the tile are skipped. */
+int wcmc_stitch_tiles(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo,
+                      const float* pbuf_a, const float* pbuf_b, int S, int C, int P, const int* coords, int B, int H, int W,
+                      float* out_rad, float* out_pbuf_a, float* out_pbuf_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

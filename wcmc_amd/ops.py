@@ -2083,3 +2083,74 @@ def step_counter_advance(state):
 def permutation_key(seed, counter, slot):
     """Host mirror of the key ``random_permutation_dev`` forms (``wcmc_permutation_key``; no GPU call)."""
     return int(lib().wcmc_permutation_key(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), int(slot)))
+
+
+# ------------------------------------------------------------------------------------------------- full-frame evaluation
+def image_eval(out, ipt, tgt, has_hit=None, eps=1e-4):
+    """The 40 image metrics of one denoised frame (``wcmc_image_eval``; test_models.py:234-251, support/metrics.py): a (2, 4, 5)
+    fp64 device tensor [comparison (out vs tgt, ipt vs tgt)][tone map (linear, _tonemap, tonemap, tonemap28)][metric (RelMSE,
+    RelL1, DSSIM, L1, MSE)].  out / ipt / tgt: fp32 (H, W, 3) device tensors of any strides (a channel-first frame passes as
+    ``frame.permute(1, 2, 0)`` without a copy); has_hit: the same form or None -- out is taken from ipt wherever it is 0."""
+    _need_cuda(out, ipt, tgt, has_hit)
+    h, w = out.shape[:2]
+    for t in (out, ipt, tgt) + ((has_hit,) if has_hit is not None else ()):
+        if t.dim() != 3 or tuple(t.shape) != (h, w, 3):
+            raise ValueError("image_eval: images must be (H, W, 3) of one size (got %s and %s)"
+                             % (tuple(out.shape), tuple(t.shape)))
+    if h < 7 or w < 7:
+        raise ValueError("image_eval: the image is %d x %d; SSIM's 7x7 window needs at least 7 x 7" % (h, w))
+    dev = out.device
+    res = torch.empty((2, 4, 5), device=dev, dtype=torch.float64)
+    nbytes = lib().wcmc_image_eval_workspace_bytes(h, w)
+    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)
+    hh = has_hit if has_hit is not None else None
+    hs = hh.stride() if hh is not None else (0, 0, 0)
+    check(lib().wcmc_image_eval(_ptr(out), *out.stride(), _ptr(ipt), *ipt.stride(), _ptr(tgt), *tgt.stride(), _ptr(hh), *hs,
+                                h, w, float(eps), _ptr(res), _ptr(ws), ws.numel() * 8, _stream()), "image_eval")
+    return res
+
+
+def check_tile_coords(coords, h, w, patch):
+    """Host check of a (B, 6) tile table (i_start, j_start, i_end, j_end, i, j) before it goes to ``stitch_tiles``: every owned
+    window lies inside the frame and inside its tile."""
+    for i0, j0, i1, j1, i, j in coords:
+        if not (0 <= i0 < i1 <= h and 0 <= j0 < j1 <= w and i <= i0 and j <= j0 and i1 <= i + patch and j1 <= j + patch):
+            raise ValueError("stitch_tiles: tile %s does not fit a %d x %d frame of %d-pixel tiles"
+                             % ((i0, j0, i1, j1, i, j), h, w, patch))
+
+
+def stitch_tiles(out, p_buffers, coords, out_rad, out_path=None, patch=128):
+    """Paste one batch of tiles into the full frame (``wcmc_stitch_tiles``; the slice loop of test_models.py:75-89).
+    out: (B, 3, ho, wo) network output ('replicate'-padded back to ``patch`` on the fly when smaller); p_buffers: None, a
+    (B, S, C, patch, patch) tensor or a dict of them; coords: device int32 (B, 6) table whose rows passed
+    ``check_tile_coords``; out_rad (3, H, W) and out_path ((S, C, H, W), or a dict of them keyed like p_buffers) are written
+    in place.  Bit-identical to the slice copies."""
+    _need_cuda(out, out_rad)
+    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
+            and coords.is_contiguous()):
+        raise RuntimeError("stitch_tiles: coords must be a contiguous device int32 (B, 6) tensor")
+    b, c3, ho, wo = out.shape
+    _, h, w = out_rad.shape
+    assert c3 == 3 and coords.shape[0] == b and out_rad.shape[0] == 3 and out_rad.is_contiguous()
+    pairs = []
+    if p_buffers is not None:
+        if isinstance(p_buffers, dict):
+            pairs = [(p_buffers[k], out_path[k]) for k in p_buffers]
+        else:
+            pairs = [(p_buffers, out_path)]
+    for pb, op in pairs:
+        _need_cuda(pb, op)
+        assert pb.dim() == 5 and pb.shape[0] == b and tuple(pb.shape[3:]) == (patch, patch) and pb.is_contiguous()
+        assert tuple(op.shape) == (pb.shape[1], pb.shape[2], h, w) and op.is_contiguous()
+    # two P-buffers of one shape per launch; anything else in further launches (the radiance is re-copied: same values)
+    groups = [pairs[i:i + 2] for i in range(0, len(pairs), 2)] or [[]]
+    if len(pairs) == 2 and pairs[0][0].shape != pairs[1][0].shape:
+        groups = [[pairs[0]], [pairs[1]]]
+    for g in groups:
+        pa, oa = g[0] if len(g) > 0 else (None, None)
+        pbb, ob = g[1] if len(g) > 1 else (None, None)
+        s, c = (pa.shape[1], pa.shape[2]) if pa is not None else (0, 0)
+        check(lib().wcmc_stitch_tiles(_ptr(out), *out.stride(), ho, wo, _ptr(pa), _ptr(pbb), s, c, patch,
+                                      ctypes.c_void_p(coords.data_ptr()), b, h, w, _ptr(out_rad), _ptr(oa), _ptr(ob),
+                                      _stream()), "stitch_tiles")
+    return out_rad, out_path

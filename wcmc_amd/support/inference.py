@@ -79,3 +79,31 @@ def crop_and_composite(out_rad, noisy_input, has_hit, patch_size=128, valid_size
     noisy_input = noisy_input[crop:-crop, crop:-crop, ...]
     has_hit = has_hit[crop:-crop, crop:-crop, ...]
     return torch.where(has_hit == 0, noisy_input, out_rad)
+
+
+def stitched_inference(interface, dataset, patch_size=128, use_llpm_buf=True):
+    """``inference`` over a ``support.datasets.FullImageDataset`` with one ``wcmc_stitch_tiles`` launch per batch in place of
+    the per-tile slice copies (bit-identical to them).  Returns ``(out_rad (3, H, W), out_path)`` on the device; out_path is
+    None, or (like the P-buffers of ``validate_batch``) a dict / tensor of (S, C, H, W)."""
+    from .. import ops
+    interface.to_eval_mode()
+    h, w = dataset.h, dataset.w
+    out_rad, out_path = None, None
+    with torch.no_grad():
+        for batch, coords in dataset.tile_batches():
+            out, p_buffers = interface.validate_batch(batch)
+            if out_rad is None:
+                out_rad = torch.zeros((3, h, w), device=out.device)
+            if not (use_llpm_buf and p_buffers is not None):
+                p_buffers = None
+            elif out_path is None:
+                if isinstance(p_buffers, dict):
+                    out_path = {key: torch.zeros((v.shape[1], v.shape[2], h, w), device=v.device)
+                                for key, v in p_buffers.items()}
+                else:
+                    out_path = torch.zeros((p_buffers.shape[1], p_buffers.shape[2], h, w), device=p_buffers.device)
+            if p_buffers is not None:
+                p_buffers = ({k: v.contiguous() for k, v in p_buffers.items()} if isinstance(p_buffers, dict)
+                             else p_buffers.contiguous())
+            ops.stitch_tiles(out, p_buffers, coords, out_rad, out_path, patch_size)
+    return out_rad, out_path
