@@ -52,7 +52,7 @@ if __name__ == "__main__":
             ops.FUSE_EMBED, ops.FUSE_FINAL = (fe and fuse), (ff and fuse)
             try:
                 # (parity_report asserts the default switches; the fused-chain switches are part of what is varied here)
-                report, _ = t.parity_report("device", True, seed=seed, pin_defaults=False, bars=(1.0, 1.0))
+                report = t.parity_report("device", True, seed=seed, pin_defaults=False)[0]
             finally:
                 ops.FUSE_EMBED, ops.FUSE_FINAL = fe, ff
                 ops.TERMS_BY_KS = {}

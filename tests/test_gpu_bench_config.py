@@ -13,8 +13,10 @@ read back from the product; ``rng='cpu'``: the reference's ``torch.randperm`` st
   * the parameter DELTAS of each Adam step against the oracle's (step 2 restarts the oracle from the product's
     weights, so that it compares two implementations of one step, not two networks a few sign ties apart).
 """
+import copy
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -32,42 +34,114 @@ from oracle.models import KPCN as OKPCN                      # noqa: E402
 from oracle.networks import PathNet as OPathNet              # noqa: E402
 
 DEV = "cuda"
-# Per-tensor gradient bar, no fallback: relative L2 and 1 - cosine against the fp32 CPU oracle, on THREE draws (weights, biases,
-# weight_g, batches and pairing keys all move with the seed) and stated as a RATIO to what exact fp32 MFMA arithmetic
-# (``--precision fp32``: one rounding per product) reaches on the same draw in the same test run -- the worst
-# tensor is the draw's as much as the arithmetic's:
-#     seed   default mode        exact fp32        ratio      (profiles/r06_grad_bar_calibration.txt, round-6 scene patches)
-#     0      3.37e-3 / 5.7e-6    3.0e-4 / 4.5e-8   11 (6.7 against the floor)     KPCN diffuse layer 0, second step
-#     1      1.82e-3 / 1.3e-6    3.9e-4 / 7.2e-8   4.6 (3.6)
-#     2      1.36e-2 / 6.6e-5    3.8e-3 / 7.4e-6   3.5                            a badly conditioned draw: one PathNet, second step
-# Bar: relative L2 <= GRAD_K x max(worst fp32 tensor of the draw, GRAD_FLOOR); 1 - cos <= (that bar)^2 / 2 (the same distance for
-# a small angle).  GRAD_FLOOR is the yardstick's own resolution: the fp32 CPU oracle is up to 4.7e-4 from an fp64 run of itself
-# (scripts/diag_grad_floor.py).  Which GEMM role carries the distance, and what a wider rung there would change, is measured in
-# profiles/r06_grad_rungs.txt (PathNet.final's one-term weight gradient, on the ill-conditioned draw); the outputs and loss
-# scalars north_star names are held at 1e-3 on every draw (measured 3.5e-4 / 2e-5).
-GRAD_K, GRAD_FLOOR = 10.0, 5e-4
-GRAD_L2, GRAD_COS = 5e-3, 1.25e-5             # (absolute form of the same bar on a well-conditioned draw: the C2 test below)
-_FP32_WORST = {}
+# Per-tensor gradient bars, no fallback, against an fp64 run of the CPU oracle (``oracle.step.train_step`` on ``.double()``
+# models and batches: independent of every HIP kernel), on THREE draws (weights, biases, weight_g, batches and pairing keys all
+# move with the seed).  The yardstick of a draw is the fp32 CPU ORACLE's own distance to fp64 (relative L2 per tensor): what fp32
+# arithmetic costs on that draw, which no product kernel can move.  (Rounds 5-6 stated the bar as a ratio to the PRODUCT's own
+# exact-fp32 run against the fp32 oracle: a defect in a kernel every mode shares -- kernel apply, the losses, weight-norm,
+# recombine, pooling, clip + Adam -- raised its own yardstick and passed.  The report files still record that bar's decision.)
+#     seed  mode        product vs fp64   fp32 oracle vs fp64   product vs fp32 oracle   (profiles/r07_grad_bar_fp64.txt: worst tensors)
+#     0     bf16x321h   3.11e-3           2.1e-4                3.12e-3      worst / max(Y, 2e-4) = 14.7
+#     1     bf16x321h   1.49e-3           2.5e-4                1.54e-3                             6.0
+#     2     bf16x321h   3.12e-2           1.9e-3                3.12e-2                            16.1   (ill-conditioned: specular weight_g)
+#     0     fp32        3.4e-4                                  3.0e-4       worst per-tensor ratio, floor 2e-4: 1.60
+#     1     fp32        4.0e-4                                  3.9e-4                                               1.69
+#     2     fp32        4.0e-3            9.3e-4                3.8e-3                                               5.31
+# (B=1, tests/test_gpu_models.py::test_full_size_step_against_oracle: exact fp32 7.9e-4 from fp64, per-tensor ratio 2.3.)
+# Exact fp32 MFMA (``--precision fp32``), per tensor: relative L2 to fp64 <= FP32_A x max(the fp32 oracle's for that tensor,
+#   FP32_FLOOR); 1 - cos <= (that bar)^2 / 2.  FP32_A = 1.5 x the worst ratio (5.31, the ill-conditioned draw; 1.6-1.7 on the
+#   others).  As good as an fp32 implementation, within a small factor.
+# Default mode: relative L2 to fp64 <= min(GRAD_K x max(Y, GRAD_FLOOR), GRAD_CEIL), Y = the fp32 oracle's WORST tensor on the
+#   draw; 1 - cos <= (that bar)^2 / 2 (the same distance for a small angle).  GRAD_K = 1.5 x the worst ratio (16.1); the floor
+#   is the fp32 oracle's own smallest worst-tensor distance (2.1e-4), low enough that a 1 % scale error fails on a
+#   well-conditioned draw (bar 6.2e-3 on seed 1).  GRAD_CEIL is held below the 3.8e-2 the rounds 5-6 bar granted on seed 2 and
+#   sits 1.12 x above the measured 3.12e-2 there -- the margin that cap leaves.
+# The outputs and loss scalars north_star names are held at 1e-3 against the fp32 oracle on every draw (measured 3.5e-4 / 2e-5).
+FP32_A, FP32_FLOOR = 8.0, 2e-4
+GRAD_K, GRAD_FLOOR, GRAD_CEIL = 25.0, 2e-4, 3.5e-2
+OLD_K, OLD_FLOOR = 10.0, 5e-4                 # rounds 5-6: ratio to the product's own exact-fp32 run (recorded, not asserted)
+GRAD_L2, GRAD_COS = 5e-3, 1.25e-5             # (absolute bar against the fp32 oracle on a well-conditioned draw: the C2 test below)
+_RUNS = {}                                    # (mode, rng, weight_norm, seed) -> parity_report's result, unperturbed runs only
+_ORACLE64 = {}                                # step 0 of the fp64 oracle per draw: it does not depend on the product
+REPORT_DIR = os.environ.get("WCMC_TEST_REPORTS", os.path.join(ROOT, "test_reports"))     # (git-ignored)
+FP64_SECONDS = [0.0, 0]                       # wall time spent in fp64 oracle steps by this process, and their number
+
+
+def _run(mode, rng_mode, weight_norm, seed):
+    """parity_report of the unperturbed step in precision `mode` (cached): (report, failures, gradients)."""
+    from wcmc_amd import ops
+    key = (mode, rng_mode, bool(weight_norm), int(seed))
+    if key not in _RUNS:
+        old = ops.PRECISION
+        ops.set_precision(mode)
+        try:
+            _RUNS[key] = parity_report(rng_mode, weight_norm, seed=seed, pin_defaults=(mode == old))
+        finally:
+            ops.set_precision(old)
+    return _RUNS[key]
 
 
 def _fp32_yardstick(weight_norm, seed):
-    """Worst per-tensor relative L2 of the same two steps in exact fp32 MFMA arithmetic (cached per draw)."""
-    key = (bool(weight_norm), int(seed))
-    if key not in _FP32_WORST:
-        from wcmc_amd import ops
-        old = ops.PRECISION
-        ops.set_precision("fp32")
-        try:
-            report, _ = parity_report("device", weight_norm, seed=seed, pin_defaults=False, bars=(1.0, 1.0))
-        finally:
-            ops.set_precision(old)
-        _FP32_WORST[key] = max(r[1] for r in report if " grad " in r[0])
-    return _FP32_WORST[key]
+    """Worst per-tensor relative L2 of the exact-fp32 run against the fp32 oracle (the rounds 5-6 yardstick)."""
+    return max(r[1] for r in _run("fp32", "device", weight_norm, seed)[0] if " grad " in r[0])
 
 
 def _max_rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+def _grads(report):
+    return [r for r in report if " grad " in r[0]]
+
+
+def fp32_mode_fails(report):
+    """The exact-fp32 bar: each tensor against fp64 within FP32_A x the fp32 oracle's own distance (or the floor)."""
+    fails = []
+    for name, _, _, _, e64, c64, y64, _ in _grads(report):
+        bar = FP32_A * max(y64, FP32_FLOOR)
+        if e64 > bar or c64 > 0.5 * bar * bar:
+            fails.append("%s: vs fp64 rel L2 %.3e, 1-cos %.2e; bar %.3e = %.0f x max(fp32 oracle %.3e, %.0e)"
+                         % (name, e64, c64, bar, FP32_A, y64, FP32_FLOOR))
+    return fails
+
+
+def default_bar(report):
+    """(bar, Y): the default mode's relative-L2 bar against fp64 on this draw, and the fp32 oracle's worst tensor Y."""
+    y = max(r[6] for r in _grads(report))
+    return min(GRAD_K * max(y, GRAD_FLOOR), GRAD_CEIL), y
+
+
+def default_mode_fails(report):
+    bar, y = default_bar(report)
+    return ["%s: vs fp64 rel L2 %.3e, 1-cos %.2e; bar %.3e (fp32 oracle's worst %.3e)" % (r[0], r[4], r[5], bar, y)
+            for r in _grads(report) if r[4] > bar or r[5] > 0.5 * bar * bar]
+
+
+def old_ratio_verdict(report, yard):
+    """What the rounds 5-6 bar decided: rel L2 to the fp32 oracle <= OLD_K x max(yard, OLD_FLOOR), 1 - cos <= bar^2 / 2, where
+    yard is the worst tensor of the PRODUCT's exact-fp32 run against the fp32 oracle on the same draw."""
+    bar = OLD_K * max(yard, OLD_FLOOR)
+    bad = [r[0] for r in _grads(report) if r[1] > bar or r[2] > 0.5 * bar * bar]
+    return bar, bad
+
+
+def write_report(fname, report, head):
+    lines = ["# %s\n" % line for line in head]
+    lines.append("# %-58s %-31s %-20s %s\n" % ("", "product vs fp64 (relL2, 1-cos)", "fp32 oracle vs fp64", "product vs fp32 oracle"))
+    for r in sorted(report, key=lambda r: -(r[4] if len(r) > 4 else r[1])):
+        if len(r) > 4:
+            lines.append("%-60s %.3e  %.2e    %.3e  %.2e   %.3e  %.2e  max-norm %.2e\n" % (r[0], r[4], r[5], r[6], r[7], r[1], r[2], r[3]))
+        else:
+            lines.append("%-60s %.3e\n" % (r[0], r[1]))
+    _write(fname, lines)
+
+
+def _summary(report):
+    g = _grads(report)
+    w = max(g, key=lambda r: r[4])
+    return ("worst tensor vs fp64 %.3e (%s); fp32 oracle's worst vs fp64 %.3e; worst vs the fp32 oracle %.3e"
+            % (w[4], w[0], max(r[6] for r in g), max(r[1] for r in g)))
 
 
 @pytest.mark.parametrize("rng_mode,weight_norm,seed", [("device", True, 0), ("device", True, 1), ("device", True, 2),
@@ -79,25 +153,121 @@ def test_benchmarked_configuration_two_steps_against_oracle(rng_mode, weight_nor
     leg).  Same bars for both.  ``rng_mode='device'`` is the switch ``bench.py`` runs with (``config.feature_mse_rng``): the pairings come from the
     keyed device bijection (``GraphedTrainStep._draw``), are read back from ``fm.static_perms`` after the replay and handed to
     the oracle; ``'cpu'`` is the reference's ``torch.randperm`` stream (``losses.py:35,50``), drawn identically on both sides."""
+    from wcmc_amd import ops
+    report, fails, _ = _run(ops.PRECISION, rng_mode, weight_norm, seed)
+    bar, y = default_bar(report)
     yard = _fp32_yardstick(weight_norm, seed)
-    l2 = GRAD_K * max(yard, GRAD_FLOOR)
-    report, fails = parity_report(rng_mode, weight_norm, seed=seed, bars=(l2, 0.5 * l2 * l2))
-    out = os.path.join(ROOT, "gpurun_out")
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, "bench_config_parity_%s%s_seed%d.txt" % (rng_mode, "" if weight_norm else "_plain", seed)), "w") as f:
-        worst = max(r[1] for r in report if " grad " in r[0])
-        f.write("# seed %d: worst gradient tensor %.3e = %.1f x exact fp32 MFMA on this draw (%.3e); bar %.3e\n" % (seed, worst, worst / yard, yard, l2))
-        for name, e, c, mx in sorted(report, key=lambda r: -r[1]):
-            f.write("%-60s relL2/err %.3e%s%s\n" % (name, e, "" if c is None else "  1-cos %.2e" % c,
-                                                    "" if mx is None else "  max-norm %.2e" % mx))
+    old_bar, old_bad = old_ratio_verdict(report, yard)
+    write_report("bench_config_parity_%s%s_seed%d.txt" % (rng_mode, "" if weight_norm else "_plain", seed), report, [
+        "seed %d, default mode: %s" % (seed, _summary(report)),
+        "bar against fp64: min(%g x max(%.3e, %g), %g) = %.3e" % (GRAD_K, y, GRAD_FLOOR, GRAD_CEIL, bar),
+        "fp64 oracle so far in this process: %d steps, %.0f s" % (FP64_SECONDS[1], FP64_SECONDS[0]),
+        "old ratio bar (rounds 5-6): %.3e against the fp32 oracle (product's exact-fp32 worst %.3e) -> %s"
+        % (old_bar, yard, "PASS" if not old_bad else "FAIL %s" % old_bad[:3])])
+    fails = fails + default_mode_fails(report)
     assert not fails, "\n".join(fails)
 
 
+def _write(fname, lines):
+    """A report file under REPORT_DIR (per-tensor rows, bars, and what the rounds 5-6 bar decided)."""
+    os.makedirs(REPORT_DIR, exist_ok=True)
+    with open(os.path.join(REPORT_DIR, fname), "w") as f:
+        f.write("".join(lines))
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_exact_fp32_mode_against_fp64_oracle(seed):
+    """The product in exact fp32 MFMA arithmetic is as good as an fp32 implementation, tensor by tensor: its distance to the fp64
+    oracle within FP32_A x the fp32 CPU oracle's (floor FP32_FLOOR).  The conv GEMMs are exact here, so this is the check that
+    holds the kernels every precision mode shares (kernel apply, FeatureMSE, the image losses, weight-norm, recombine, the P-buffer
+    cat, pooling and upsampling, clip and Adam): a 1 % scale error in any of their backwards fails it
+    (test_the_gradient_bars_catch_a_one_percent_gradient_error)."""
+    report, fails, _ = _run("fp32", "device", True, seed)
+    f32 = fp32_mode_fails(report)
+    write_report("bench_config_parity_fp32_seed%d.txt" % seed, report, [
+        "seed %d, exact fp32 MFMA: %s" % (seed, _summary(report)),
+        "bar per tensor: %g x max(fp32 oracle's distance to fp64, %g); %d tensors over it" % (FP32_A, FP32_FLOOR, len(f32))])
+    fails = fails + f32
+    assert not fails, "\n".join(fails)
+
+
+def _scaled_backward(cls, counter):
+    """cls.backward with every gradient it returns scaled by 1 + 1e-2, in place (a defect of 1 % in that op's backward)."""
+    orig = cls.backward
+
+    def backward(ctx, *g):
+        counter[0] += 1
+        out = orig(ctx, *g)
+        for t in (out if isinstance(out, tuple) else (out,)):
+            if isinstance(t, torch.Tensor):
+                t.mul_(1.0 + 1e-2)
+        return out
+    return orig, staticmethod(backward)
+
+
+def test_the_gradient_bars_catch_a_one_percent_gradient_error():
+    """The bars have teeth: one op's Python-level backward scales its gradients by 1 + 1e-2 (patched before the step is
+    captured, restored after), and the report must FAIL.  A shared op (kernel apply: every mode runs it) must fail the exact-fp32
+    check; the rounds 5-6 ratio bar, whose yardstick ran through the same op, is recorded for the same defect.  An op of the
+    split-bf16 path only (the KPCN / U-Net conv chains) must fail the default-mode check.  Every mutation must have run (the hook
+    was called) and moved the gradients (against the unperturbed run of the same draw): none is vacuous."""
+    from wcmc_amd import ops
+    seed, mode = 1, ops.PRECISION
+    lines = []
+
+    def mutated(cls, m):
+        counter = [0]
+        orig, patched = _scaled_backward(cls, counter)
+        old = ops.PRECISION
+        ops.set_precision(m)
+        cls.backward = patched
+        try:
+            rep = parity_report("device", True, seed=seed, pin_defaults=False)
+        finally:
+            cls.backward = orig
+            ops.set_precision(old)
+        assert counter[0] > 0, "%s.backward never ran in the benchmarked step (%s)" % (cls.__name__, m)
+        moved = max(rel_l2(rep[2][k], g) for k, g in _run(m, "device", True, seed)[2].items())
+        assert moved > 2e-3, "the %s mutation did not move the gradients (%s): %.3e" % (cls.__name__, m, moved)
+        return rep, moved
+
+    # a shared op, exact-fp32 mode: the exact-fp32 check fails
+    rep32, m32 = mutated(ops._KernelApply, "fp32")
+    f32 = fp32_mode_fails(rep32[0])
+    lines.append("_KernelApply x 1.01, fp32: gradients moved %.3e from the unperturbed run; exact-fp32 check: %d tensors fail%s"
+                 % (m32, len(f32), "" if not f32 else " (first: %s)" % f32[0]))
+    # the same defect in the default mode, judged by the old ratio bar (its yardstick: the mutated exact-fp32 run) and the new one
+    repd, md = mutated(ops._KernelApply, mode)
+    yard = max(r[1] for r in _grads(rep32[0]))
+    old_bar, old_bad = old_ratio_verdict(repd[0], yard)
+    fd = default_mode_fails(repd[0])
+    lines.append("_KernelApply x 1.01, %s: gradients moved %.3e; old ratio bar %.3e (mutated exact-fp32 yardstick %.3e) -> %s; "
+                 "default-mode check against fp64: %d tensors fail" % (mode, md, old_bar, yard, "PASS" if not old_bad else "FAIL", len(fd)))
+    # an op of the split-bf16 path only, default mode: the default-mode check fails
+    reps, ms = mutated(ops._ConvChainX, mode)
+    fs = default_mode_fails(reps[0])
+    lines.append("_ConvChainX x 1.01, %s: gradients moved %.3e; default-mode check against fp64: %d tensors fail%s"
+                 % (mode, ms, len(fs), "" if not fs else " (first: %s)" % fs[0]))
+    _write("bench_config_mutations.txt", [line + "\n" for line in lines])
+    assert f32, "a 1 % error in kernel apply's backward passes the exact-fp32 check"
+    assert fd, "a 1 % error in kernel apply's backward passes the default-mode check"
+    assert fs, "a 1 % error in the split-bf16 conv chains' backward passes the default-mode check"
+
+
+def _double(batch):
+    return {k: v.double() if v.is_floating_point() else v for k, v in batch.items()}
+
+
 def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
-    """The comparison itself; returns (report rows, failures).  seed: shifts the weights' seed, the bias / weight_g draws, the batches
-    and the pairing keys together (scripts/calibrate_grad_bar.py runs several to put the gradient bar on more than one draw).
-    bars: (relative L2, 1 - cos) per gradient tensor; default: the module's absolute pair."""
-    grad_l2, grad_cos = bars if bars is not None else (GRAD_L2, GRAD_COS)
+    """The comparison itself; returns (report rows, failures, gradients).  seed: shifts the weights' seed, the bias / weight_g draws,
+    the batches and the pairing keys together (scripts/calibrate_grad_bar.py runs several to put the gradient bars on more than one
+    draw).  Two oracles run beside the product on the same weights, batches and pairings: the fp32 CPU oracle (what the reference
+    computes) and the same oracle in fp64 (the yardstick of both).  Gradient rows: (name, relative L2, 1 - cos, max-norm error of
+    the product against the fp32 oracle, relative L2 and 1 - cos of the product against fp64, relative L2 and 1 - cos of the fp32
+    oracle against fp64); the other rows: (name, error, None, None / delta error in lr).  failures: losses, outputs and Adam deltas
+    against the fp32 oracle, and the per-tensor gradient bar against it when ``bars`` = (relative L2, 1 - cos) is given; the
+    callers hold the gradients against fp64 (``fp32_mode_fails``, ``default_mode_fails``).  gradients: {(step, model, name): the
+    product's post-clip gradient on the CPU}."""
     import bench
     from wcmc_amd import ops
     from wcmc_amd.graph import GraphedTrainStep
@@ -123,6 +293,14 @@ def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
                     p.mul_((torch.rand(p.shape, generator=g) * 0.6 + 0.7).to(device))
         omods[k].load_state_dict({n: v.detach().cpu().clone() for n, v in m.state_dict().items()})
     oopt = {"optim_" + k: torch.optim.Adam(m.parameters(), lr=1e-4) for k, m in omods.items()}
+    # the fp64 oracle: same weights, its own Adam moments
+    with torch.random.fork_rng(devices=[]):                               # (its initialisation draws leave the CPU stream alone)
+        o64 = {"dncnn": OKPCN(39), "backbone_diffuse": OPathNet(36, weight_norm=weight_norm),
+               "backbone_specular": OPathNet(36, weight_norm=weight_norm)}
+    for k in o64:
+        o64[k].load_state_dict(omods[k].state_dict())
+        o64[k].double()
+    oopt64 = {"optim_" + k: torch.optim.Adam(m.parameters(), lr=1e-4) for k, m in o64.items()}
     cfg = dict(use_llpm_buf=True, manif_learn=True, train_branches=True, disentanglement_option="m11r11", w_manif=0.1)
     batches = [make_batch(B, S, H, seed=40 + i + 10 * seed, device="cpu") for i in range(2)]
     dbatches = [{k: v.to(device) for k, v in b.items()} for b in batches]
@@ -139,6 +317,7 @@ def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
     torch.manual_seed(1234 + seed)                                        # the graph draws the same stream, same order
     report, fails = [], []
     ograds = [{}, {}]
+    hgrads = {}
     lr = 1e-4
     p_prev = {mn: dict(d) for mn, d in p_start.items()}
     fm = itf.loss_funcs["l_manif"]
@@ -161,6 +340,22 @@ def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
             graphed(dbatches[step])
             torch.cuda.synchronize()
             assert torch.equal(fm.static_perms[1][0].cpu(), perms[step][1][0])
+        # the fp64 oracle on the pairings just used; its first step depends on the draw alone (cached)
+        key64 = (rng_mode, bool(weight_norm), int(seed))
+        hit = _ORACLE64.get(key64) if step == 0 else None
+        if hit is not None and all(torch.equal(a, b) for pa, pb in zip(hit[0], perms[0]) for a, b in zip(pa, pb)) and \
+                all(torch.equal(hit[1][mn][k], v) for mn, d in p_start.items() for k, v in d.items()):
+            g64 = hit[2]
+            for k, o in oopt64.items():
+                o.load_state_dict(copy.deepcopy(hit[3][k]))
+        else:
+            t0 = time.time()
+            ostep.train_step(o64, oopt64, _double(batches[step]), cfg, perms[step])
+            FP64_SECONDS[0] += time.time() - t0
+            FP64_SECONDS[1] += 1
+            g64 = {mn: [q.grad.detach().clone() for q in o64[mn].parameters()] for mn in o64}
+            if step == 0:
+                _ORACLE64[key64] = (perms[0], p_start, g64, {k: copy.deepcopy(o.state_dict()) for k, o in oopt64.items()})
         for k, v in loss_o.items():
             np.testing.assert_allclose(graphed.losses[k].item(), v.item(), rtol=1e-3, err_msg="step %d %s" % (step, k))
         for k in ("radiance", "diffuse", "specular"):
@@ -169,15 +364,17 @@ def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
                 fails.append("step %d denoised %s: %.3e" % (step, k, e))
             report.append(("step%d out %s" % (step, k), e, None, None))
         for mn in omods:
-            for (k, p), (_, q) in zip(hmods[mn].named_parameters(), omods[mn].named_parameters()):
-                got = p.grad.clamp(-1.0, 1.0)          # the oracle's .grad is post clip_grad_value_ (interfaces.py:260-261)
+            for (k, p), (_, q), r in zip(hmods[mn].named_parameters(), omods[mn].named_parameters(), g64[mn]):
+                got = p.grad.clamp(-1.0, 1.0).cpu()    # the oracle's .grad is post clip_grad_value_ (interfaces.py:260-261)
                 ograds[step][(mn, k)] = q.grad.detach().clone()
-                try:
-                    e = assert_grad_close(got, q.grad, what="step %d grad %s %s" % (step, mn, k), l2=grad_l2, cos=grad_cos)
-                except AssertionError as err:
-                    fails.append(str(err))
-                    e = rel_l2(got, q.grad)
-                report.append(("step%d grad %s %s" % (step, mn, k), e, 1.0 - cosine(got, q.grad), _max_rel(got, q.grad)))
+                hgrads[(step, mn, k)] = got
+                if bars is not None:
+                    try:
+                        assert_grad_close(got, q.grad, what="step %d grad %s %s" % (step, mn, k), l2=bars[0], cos=bars[1])
+                    except AssertionError as err:
+                        fails.append(str(err))
+                report.append(("step%d grad %s %s" % (step, mn, k), rel_l2(got, q.grad), 1.0 - cosine(got, q.grad), _max_rel(got, q.grad),
+                               rel_l2(got, r), 1.0 - cosine(got, r), rel_l2(q.grad, r), 1.0 - cosine(q.grad, r)))
         # The Adam step itself: parameter DELTAS of this step against the oracle's.  Adam's first step is
         # -lr * g / (|g| + eps) = -lr * sign(g): an entry whose gradient is smaller than the gradient error may go the other
         # way (2 * lr apart) in two correct implementations.  So (i) entries whose oracle gradient is well conditioned (>= half
@@ -214,11 +411,12 @@ def parity_report(rng_mode, weight_norm, seed=0, pin_defaults=True, bars=None):
         # L2 on the KPCN input layer) instead of two implementations of the same step.  Adam's moments stay the oracle's own.
         for mn in omods:
             with torch.no_grad():
-                for (k, p), (_, q) in zip(hmods[mn].named_parameters(), omods[mn].named_parameters()):
+                for (k, p), (_, q), q64 in zip(hmods[mn].named_parameters(), omods[mn].named_parameters(), o64[mn].parameters()):
                     q.copy_(p.detach().cpu())
+                    q64.copy_(p.detach().cpu().double())
                     p_prev[mn][k] = p.detach().cpu().clone()
     graphed.close()
-    return report, fails
+    return report, fails, hgrads
 
 
 def test_c2_vanilla_full_size_graphed_step_against_oracle():

@@ -1500,6 +1500,52 @@ def test_deferred_reduction_never_writes_into_memory_that_is_not_the_gradients(w
     del fo
 
 
+@pytest.mark.parametrize("weight_kind", ["scaled", "leaf"])
+def test_deferred_reduction_of_a_weight_that_is_neither_a_parameter_nor_weight_normalised(weight_kind):
+    """a layer whose weight is not a Parameter but whose bias has a registered bucket view.  Only the effective weight
+    of a weight-normalised layer may have its slab reduction deferred (the weight-norm node flushes before it reads dw); any other
+    weight's consumer reads dw at once -- a scaled (or tied, or parametrised) weight's backward multiplies it, AccumulateGrad of a
+    plain leaf clones it while the pending entry still holds it.  Functional ``ops.conv_chain`` with such weights, inside a
+    ``deferred_wgrad_reduce()`` scope: the gradients must equal the un-deferred run's bit for bit."""
+    from wcmc_amd.modules import ConvChain
+    from wcmc_amd.optim import FusedClipAdam
+    o = ops()
+    torch.manual_seed(9)
+    mod = ConvChain(64, 64, ksize=3, width=64, depth=3, pad=True, output_type="relu", weight_norm=False).to(DEV)
+    fo = FusedClipAdam({"m": mod}, {"optim_m": torch.optim.Adam(mod.parameters(), lr=1e-3)})      # the biases' bucket views
+    x = gen(4, 64, 40, 36, seed=74).to(DEV)
+    g = gen(4, 64, 40, 36, seed=75).to(DEV)
+    leaves = [c.weight.detach().clone().requires_grad_(True) for c in mod.layers]
+    acts = ["relu"] * 3
+
+    def grads(defer):
+        mod.zero_grad()
+        for w in leaves:
+            w.grad = None
+        o.release_grad_sinks(list(mod.parameters()))
+        params = []
+        for c, w in zip(mod.layers, leaves):
+            params += [c.weight * 2.0 if weight_kind == "scaled" else w, c.bias]
+        y = o.conv_chain(x, 3, 1, acts, params)
+        if defer:
+            with o.deferred_wgrad_reduce():
+                y.backward(g)
+                pend = sum(len(v[1]) for v in o._DEFERRED.values())
+        else:
+            pend = 0
+            y.backward(g)
+        torch.cuda.synchronize()
+        held = [c.weight for c in mod.layers] if weight_kind == "scaled" else leaves
+        return [t.grad.clone() for t in held] + [c.bias.grad.clone() for c in mod.layers], pend
+
+    want, _ = grads(False)
+    got, pend = grads(True)
+    assert pend == 0, "%d slab reductions of weights whose consumer does not flush were deferred" % pend
+    for i, (a, b) in enumerate(zip(want, got)):
+        assert torch.equal(a, b), "%s weights: %s %d differs under deferred_wgrad_reduce" % (weight_kind, "weight" if i < 3 else "bias", i % 3)
+    del fo
+
+
 @pytest.mark.parametrize("kind,cls", [("smape", "SMAPE"), ("tonemapped_mse", "TonemappedMSE"), ("tonemapped_relative_mse", "TonemappedRelativeMSE")])
 def test_sample_interface_losses_match_the_oracle(kind, cls):
     """SMAPE / TonemappedMSE / TonemappedRelativeMSE (support/losses.py:267-320) as HIP passes: value and dL/dx against the oracle's

@@ -547,6 +547,12 @@ def _param_ptr(t):
     return t.data_ptr() if isinstance(t, torch.nn.Parameter) else 0
 
 
+def _flushed_by_consumer(w):
+    """True when the gradient of weight `w` is read by a node that flushes the deferred slab reductions first: `w` is an output
+    of ``_WeightNormMulti`` itself (defined below; looked up when called)."""
+    return isinstance(w.grad_fn, _WeightNormMulti._backward_cls)
+
+
 # ---- weight normalisation ------------------------------------------------------------------
 class _WeightNormMulti(torch.autograd.Function):
     """``w_l = g_l * v_l / ||v_l||`` for ALL weight-normalised layers of a model as one node: one launch forms every effective
@@ -949,10 +955,13 @@ def _reduce_multi(entries):
                                                        _stream()), "conv2d_wgrad_reduce_multi")
 
 
-def conv2d_wgrad_x_raw(xs, xdims, dys, cout, ks, pad, weight_shape, want_bias=True, colsum_part=None, terms=None, sinks=(0, 0)):
+def conv2d_wgrad_x_raw(xs, xdims, dys, cout, ks, pad, weight_shape, want_bias=True, colsum_part=None, terms=None, sinks=(0, 0),
+                       dw_flushed=False):
     """dw (and db) of one layer.  colsum_part: the per-tile column sums of dys that the launch producing dys left; the bias
     gradient is then finished by the slab-reduction launch itself (no column-sum pass, no finish launch).  sinks: data_ptr of the
-    weight / bias PARAMETER (0: none) -- their gradients go straight into the optimiser's bucket where one is registered."""
+    weight / bias PARAMETER (0: none) -- their gradients go straight into the optimiser's bucket where one is registered.
+    dw_flushed: the weight is an output of ``_WeightNormMulti``, whose backward flushes this stream's deferred reductions before
+    it reads dw (``_flushed_by_consumer``)."""
     n, cin, h, w = xdims
     ho, wo = h + 2 * pad - ks + 1, w + 2 * pad - ks + 1
     nbytes = lib().wcmc_conv2d_wgrad_bf16x3_workspace_bytes(n, ho, wo, cout, cin, ks)
@@ -964,11 +973,12 @@ def conv2d_wgrad_x_raw(xs, xdims, dys, cout, ks, pad, weight_shape, want_bias=Tr
     terms = wgrad_terms() if terms is None else terms
     # A reduction may be deferred only where the memory it will write is certain to be the gradient's when it runs:
     # a bucket view (the optimiser's memory; AccumulateGrad adopts the tensor -- a parameter that already has a .grad, or needs
-    # none, gets a fresh tensor from _sink_ex, which autograd adds into .grad or drops at once), or the weight gradient of a
-    # NON-leaf weight (sinks[0] == 0: the effective weight of a weight-normalised layer, consumed by the weight-norm node, which
-    # flushes first; the entry then holds the tensor itself).  A fresh tensor for a leaf is reduced inline.  And never on a
-    # weight-gradient side stream: the reader flushes ITS stream's entries.
-    safe = (dw_view or sinks[0] == 0) and db_view
+    # none, gets a fresh tensor from _sink_ex, which autograd adds into .grad or drops at once), or the weight gradient of an
+    # effective weight of a weight-normalised layer (dw_flushed: consumed by the weight-norm node, which flushes first; the entry
+    # then holds the tensor itself).  Any other weight -- a leaf that is no Parameter, a scaled, tied or otherwise computed
+    # tensor -- is reduced inline: its consumer reads dw without flushing.  And never on a weight-gradient side
+    # stream: the reader flushes ITS stream's entries.
+    safe = (dw_view or dw_flushed) and db_view
     if (_PROFILER is None and _DEFERRED is not None and safe and nbytes <= DEFER_MAX_BYTES and (db is None or colsum_part is not None)
             and not _on_side_stream()):
         check(lib().wcmc_conv2d_wgrad_bf16x3(*args, 1, cs, terms, _stream()), "conv2d_wgrad_bf16x3")      # the GEMM now,
@@ -1092,6 +1102,7 @@ def _chainx_backward(ctx, dy, need_dx, dys=None, part=None):
     wterms, dterms = ctx.terms
     bptrs = getattr(ctx, "bias_ptrs", None) or [0] * nl
     sink_of = lambda l: (ws[l].data_ptr() if isinstance(ws[l], torch.nn.Parameter) else 0, bptrs[l])
+    flushed = [_flushed_by_consumer(w) for w in ws]
     pack1 = (lambda l: wp1[l]) if wp1 is not None else (lambda l: _pack_x(ws[l], _dgrad_mode(dterms)))
     for l in range(nl - 1, -1, -1):
         wt = ws[l]
@@ -1100,14 +1111,14 @@ def _chainx_backward(ctx, dy, need_dx, dys=None, part=None):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 dw, db = conv2d_wgrad_x_raw(xs[l], dims[l], dys, cout, ks, pad, wt.shape, want_bias=part is None,
-                                            colsum_part=part, terms=wterms, sinks=sink_of(l))
+                                            colsum_part=part, terms=wterms, sinks=sink_of(l), dw_flushed=flushed[l])
             dw.record_stream(main)
             db.record_stream(main)
             keep.append(dys)
             keep.append(part)
         else:
             dw, db = conv2d_wgrad_x_raw(xs[l], dims[l], dys, cout, ks, pad, wt.shape, want_bias=part is None,
-                                        colsum_part=part, terms=wterms, sinks=sink_of(l))
+                                        colsum_part=part, terms=wterms, sinks=sink_of(l), dw_flushed=flushed[l])
         grads[2 * l], grads[2 * l + 1] = dw, db
         if (l == 1 and need_dx and ks == 1 and pad == 0 and
                 lib().wcmc_conv1x1_pair_supported(cout, wt.shape[1], ws[0].shape[1])):
