@@ -1,5 +1,6 @@
 // Kernels shared by the fp32 (conv.hip) and split-bf16 (conv_bf16x3.hip) convolution paths.
-// `static`: each translation unit gets its own device copy (the library is built without -fgpu-rdc).
+// `static`: each translation unit gets its own device copy (the library is built without -fgpu-rdc) -- of ALL of them, used or not:
+// include this header only in the units that launch from it.
 #pragma once
 #include "common.h"
 
