@@ -1,5 +1,5 @@
 """VGPR / spill / LDS numbers of the gfx950 kernels in one object file (no GPU needed).
-   python3 scripts/kernel_regs.py wcmc_amd/csrc/conv_bf16x3.o [name filter]"""
+   python3 scripts/kernel_regs.py wcmc_amd/csrc/bf16x3_wgrad.o [name filter]        (any object of csrc: one bf16x3_*.o per kernel family)"""
 import os, re, shutil, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 obj = sys.argv[1]

@@ -1,7 +1,8 @@
 // What the split-bf16 ("bf16x3") convolution units share: conv_bf16x3.hip (its header comment describes the operand split and the
-// tensor / weight layouts), bf16x3_igemm.hip and bf16x3_halo64.hip.  Every kernel template is instantiated in exactly ONE unit
-// (DESIGN.md 4.2): a family is launched through its launch entry declared at the end of this header, never by naming its kernel
-// from another unit.
+// tensor / weight layouts; it holds the glue kernels, the plans and every C entry) and one unit per GEMM kernel family --
+// bf16x3_igemm.hip, bf16x3_halo.hip, bf16x3_halo64.hip, bf16x3_halo3.hip, bf16x3_pw.hip, bf16x3_wgrad.hip.  Every kernel template is
+// instantiated in exactly ONE unit: a family is launched through its launch entry declared at the end of this
+// header, never by naming its kernel from another unit.
 #pragma once
 #include "common.h"
 
@@ -111,6 +112,39 @@ struct XIgemmParams {
   int Cout2, act2, Kt2; float slope2; unsigned wp2_bytes, y2_bytes;
 };
 
+// Parameter blocks of the weight-gradient kernels (bf16x3_wgrad.hip; wcmc_conv2d_wgrad_bf16x3 fills them): one tap per block ...
+struct XWgradParams {
+  const u16* x; int N, H, W, Cin, Cpi;
+  const u16* dy; int Ho, Wo, Cout, Cpo;
+  int ks, pad;
+  float* slabs; int S; int64_t M, pix_per_split;
+  int Np, Cq, coBlocks, ciBlocks;
+  unsigned x_bytes, dy_bytes;
+  int xps, yps;                     // pixel stride (bytes) of x / dy: 4 * Cp for a split tensor, 2 * Cp for a single bf16 plane
+};
+// ... and one filter row per block
+struct XWRowsParams {
+  const u16* x; int N, H, W, Cpi;
+  const u16* dy; int Ho, Wo, Cpo;
+  int pad;
+  float* slabs; int S, rps, R;
+  float* dbg;                       // clock-probe build only
+  int prio;                         // rows8: iteration (of 14 per stage) at which waves 0-3 hand the priority to waves 4-7; 0 = off
+  int Np, Cq, coBlocks, ciBlocks;
+  unsigned x_bytes, dy_bytes;
+  int xps, yps;                     // pixel stride (bytes) of x / dy: 4 * Cp for a split tensor, 2 * Cp for a single bf16 plane
+};
+// LDS row stride (u16) of a CH-channel tile: bytes = odd multiple of 32 (conflict-free transposing reads);
+// the pad vectors of a row are filled by DMA lanes with an out-of-range source (zeros).
+constexpr int xwr_stride(int ch) { return ((ch / 16) | 1) * 16; }
+// dynamic LDS of the filter-row instance <ks, tm, nw, pl> (as xwr_lds_bytes of bf16x3_wgrad.hip): x_plan_wgrad sizes its splits by it
+static size_t xwr_lds_bytes_rt(int ks, int tm, int nw, int pl = 2) {
+  const int nvec = pl * 64 * (xwr_stride(tm * 16) / 8) + pl * (64 + ks - 1) * (xwr_stride(nw * 16) / 8);
+  const int ni = (nvec + nw * 64 - 1) / (nw * 64);
+  const size_t stage = (size_t)2 * ni * nw * 64 * 16, red = (size_t)tm * 16 * (nw * 16 + 4) * sizeof(float);
+  return stage > red ? stage : red;
+}
+
 // Workgroup barrier for kernels that keep LDS-DMA in flight across it: __syncthreads() carries a release fence,
 // for which hipcc waits for EVERY outstanding LDS-DMA (vmcnt(0)); the rings of those kernels order their DMA by explicit counts.
 __device__ __forceinline__ void pw_barrier() {
@@ -124,7 +158,17 @@ int x_env_on(const char* name);           // conv_bf16x3.hip: switch is ON unles
 // ------------------------------------------------------------------ launch entries, one per family (its own unit defines it)
 // nt = x_pick_nt(p.Np / 16): cout tiles per block, one of {7, 4, 2, 1}
 int launch_xigemm(int nt, const XIgemmParams& p, hipStream_t stream);       // bf16x3_igemm.hip; halo plans go on to launch_xhalo
-int launch_xhalo(int nt, const XIgemmParams& p, hipStream_t stream);        // conv_bf16x3.hip; 5x5 plans of the 64-pixel kernel go on to launch_xhalo64
+int launch_xhalo(int nt, const XIgemmParams& p, hipStream_t stream);        // bf16x3_halo.hip; 5x5 plans of the 64-pixel kernel go on to launch_xhalo64
 int launch_xhalo64(int nt, const XIgemmParams& p, hipStream_t stream);      // bf16x3_halo64.hip
+// bf16x3_halo3.hip: the 3x3 plans of conv_halo3_bf16x3_kernel
+bool x_halo3_ok(const XIgemmParams& p);
+int launch_xhalo3(const XIgemmParams& p, hipStream_t stream);
+// bf16x3_pw.hip: x_plan_pw picks the pointwise instance (ntw waves, u 16-byte units per pixel) or says no; launch_xpw sets p.y_bytes / p.m_bytes
+bool x_plan_pw(const XIgemmParams& p, int* ntw, int* u);
+int launch_xpw(XIgemmParams& p, int ntw, int u, hipStream_t stream);
+int launch_xpw_pair(int kind, const XIgemmParams& p, hipStream_t stream);      // kind = x_pair_kind(...): 1..3, the fused two-layer instances
+// bf16x3_wgrad.hip; planes: 2 = three MFMAs per product, 1 = the hi planes only
+int launch_xwgrad(int tm, int planes, const XWgradParams& p, hipStream_t stream);                            // tm = XWgradPlan::TM: 7 or 4
+int launch_xwgrad_rows(int ks, int tm, int nw, int planes, const XWRowsParams& p, hipStream_t stream);      // (tm, nw) = XWgradPlan::rTM, rNW
 
 }  // namespace wcmc

@@ -772,7 +772,7 @@ def _chain_out_terms(ks, act_last, cin_last, cout_last, pair):
 
 def _igemm_class(cin, cout, ks, dims=None, terms=3):
     """Profiler class of a split-bf16 GEMM launch = the kernel the library's plan picks for it
-    (csrc/conv_bf16x3.hip: x_plan_k, x_pick_nt; csrc/bf16x3_halo64.hip: launch_xhalo64), so that a class average is one kernel's average.
+    (csrc/conv_bf16x3.hip: x_plan_k, x_pick_nt; csrc/bf16x3_pw.hip: x_plan_pw; csrc/bf16x3_halo3.hip: x_halo3_ok; csrc/bf16x3_halo64.hip: launch_xhalo64), so that a class average is one kernel's average.
     dims = (n, ho, wo) of the output selects between the two tile heights of the 5x5 kernel; terms = 2 (the data gradient of
     the default mode) runs the AP = 1 instances where the plan grants them: classes with the suffix "_x2"; terms = 1 (the output
     layers' forward of the default mode): "_x1"."""
