@@ -539,6 +539,34 @@ int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float
                                float* specular_buffer, float* albedo, float* paths, float* target_diffuse,
                                float* target_specular, float* target_total, void* stream);
 
+/* ---------------------------------------------------------------- patch-sampling probability maps
+ * support/datasets.py: gradient_importance_map :17-36 and the `_prob_imp` block of DenoiseDataset._offline_preprocess
+ * :697-715 (with LinearToSrgb(ToneMap(., 1.5)), support/utils.py:44-57); the NaN / Inf rule of :623-624.  Dense,
+ * contiguous fp32 device buffers in the reference's numpy layouts.  No atomics: every result is bitwise reproducible.
+ *
+ * wcmc_reflect_index: the source index of position i (any int) of a line of n >= 1 entries under scipy's boundary mode
+ *   'reflect' (d c b a | a b c d | d c b a, period 2n; numpy.pad's 'symmetric') -- the map the Gaussian passes use.  Host only.
+ * wcmc_importance_map: img (H, W, C), C = 1 or 3 -> out (H, W):
+ *   per channel scipy.ndimage.gaussian_filter(x, 31) (249 taps per axis, axis 0 first, mode 'reflect', fp64 accumulation in
+ *   scipy's order, rounded to fp32 between the passes), sobel along both axes with mode 'nearest', the root of the sum of squares
+ *   over the channels, then (v - min) / (max - min + 1e-5).
+ * wcmc_sampling_prob: raw (H, W, S, C >= 38 + 11*(max_depth+1)), gt (H, W, 9), both sanitised -> out (H - patch, W - patch):
+ *   prob = 0.3 * importance_map(lum) + 0.2 * importance_map(normal) + 0.5 * mat, cropped by patch/2 at the top / left and
+ *   patch - patch/2 at the bottom / right, divided by (sum + 1e-5).  lum: luminance (0.2126, 0.7152, 0.0722) of
+ *   LinearToSrgb(ToneMap(gt[..., :3], 1.5)); normal: sample mean of raw channels 17..19 (idx_g['normal'], :232-248; the s-buffer's
+ *   columns 20:23 of _preprocess_sbmc, :363-485) * 0.5 + 0.5; mat = (diffuse + 4 glossy + 2 specular) / 7 from the sample means of
+ *   bits 2, 3, 4 of raw channel 24 + 6*(max_depth+1) (idx_sbmc['bounce_types'] :249-255, bounce 0: the p-buffer's columns 48, 54, 60).
+ *   H and W must exceed patch.
+ * wcmc_sanitize: x[i] <- 1e38 where x[i] is NaN, +-Inf or >= 1e38 (:623-624), in place. */
+int wcmc_reflect_index(int i, int n);
+size_t wcmc_importance_map_workspace_bytes(int H, int W, int C);
+int wcmc_importance_map(const float* img, int H, int W, int C, float* out, void* workspace, size_t workspace_bytes,
+                        void* stream);
+size_t wcmc_sampling_prob_workspace_bytes(int H, int W, int patch);
+int wcmc_sampling_prob(const float* raw, const float* gt, int H, int W, int S, int C, int max_depth, int patch, float* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int wcmc_sanitize(float* x, int64_t n, void* stream);
+
 /* ---------------------------------------------------------------- full-frame evaluation
  * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
  * (scene, spp) cell.  out / ipt / tgt: fp32 (H, W, 3) images, element (y, x, c) at p[y*sh + x*sw + c*sc] (any int64

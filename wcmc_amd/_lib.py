@@ -107,6 +107,12 @@ SIGNATURES = {
     "wcmc_preprocess_kpcn": (I, [P, I, I, I, I, I, P, P, Z, P]),
     "wcmc_gradients": (I, [P, I, I, I, P, P]),
     "wcmc_assemble_kpcn_patches": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "wcmc_reflect_index": (I, [I, I]),
+    "wcmc_importance_map_workspace_bytes": (Z, [I, I, I]),
+    "wcmc_importance_map": (I, [P, I, I, I, P, P, Z, P]),
+    "wcmc_sampling_prob_workspace_bytes": (Z, [I, I, I]),
+    "wcmc_sampling_prob": (I, [P, P, I, I, I, I, I, I, P, P, Z, P]),
+    "wcmc_sanitize": (I, [P, L, P]),
     "wcmc_image_eval_workspace_bytes": (Z, [I, I]),
     "wcmc_image_eval": (I, [P, L, L, L, P, L, L, L, P, L, L, L, P, L, L, L, I, I, D, P, P, Z, P]),
     "wcmc_stitch_tiles": (I, [P, L, L, L, L, I, I, P, P, I, I, I, P, I, I, I, P, P, P, P]),

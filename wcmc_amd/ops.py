@@ -2065,6 +2065,55 @@ def gradients(buf):
     return out
 
 
+def reflect_index(i, n):
+    """Source index of position ``i`` of a line of ``n`` entries under scipy's 'reflect' boundary (``wcmc_reflect_index``: the
+    map the Gaussian passes of ``importance_map`` use; no GPU call)."""
+    return int(lib().wcmc_reflect_index(int(i), int(n)))
+
+
+def importance_map(img):
+    """``gradient_importance_map`` (datasets.py:17-36): (H, W) or (H, W, 3) -> (H, W) in [0, 1]."""
+    if img.dim() == 2:
+        h, w, c = img.shape[0], img.shape[1], 1
+    elif img.dim() == 3 and img.shape[2] in (1, 3):
+        h, w, c = img.shape
+    else:
+        raise ValueError("importance_map: the image should be (H, W) or (H, W, 3), got %s" % (tuple(img.shape),))
+    _need_dense(img, img.dim())
+    out = torch.empty((h, w), device=img.device, dtype=torch.float32)
+    nbytes = lib().wcmc_importance_map_workspace_bytes(h, w, c)
+    ws = torch.empty((nbytes + 3) // 4, device=img.device, dtype=torch.float32)
+    check(lib().wcmc_importance_map(_ptr(img), h, w, c, _ptr(out), _ptr(ws), ws.numel() * 4, _stream()), "importance_map")
+    return out
+
+
+def sampling_prob(raw, gt, patch_size=128, max_depth=5):
+    """The patch-sampling map of ``_offline_preprocess`` (datasets.py:697-715): sanitised raw (H, W, S, 104) and gt (H, W, 9)
+    -> (H - patch_size, W - patch_size), a distribution over patch origins."""
+    _need_dense(raw, 4)
+    _need_dense(gt, 3)
+    h, w, s, c = raw.shape
+    if tuple(gt.shape) != (h, w, 9):
+        raise ValueError("sampling_prob: gt should be (%d, %d, 9), got %s" % (h, w, tuple(gt.shape)))
+    if h <= patch_size or w <= patch_size:
+        raise ValueError("sampling_prob: the image (%d x %d) must be larger than the patch (%d) in both dimensions"
+                         % (h, w, patch_size))
+    out = torch.empty((h - patch_size, w - patch_size), device=raw.device, dtype=torch.float32)
+    nbytes = lib().wcmc_sampling_prob_workspace_bytes(h, w, patch_size)
+    ws = torch.empty((nbytes + 7) // 8, device=raw.device, dtype=torch.float64)
+    check(lib().wcmc_sampling_prob(_ptr(raw), _ptr(gt), h, w, s, c, max_depth, patch_size, _ptr(out), _ptr(ws), ws.numel() * 8,
+                                   _stream()), "sampling_prob")
+    return out
+
+
+def sanitize_(x):
+    """NaN / Inf / >= 1e38 -> 1e38 in place (datasets.py:623-624)."""
+    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("sanitize_ takes a contiguous fp32 CUDA tensor (got %s %s); there is no CPU path" % (x.device, x.dtype))
+    check(lib().wcmc_sanitize(_ptr(x), x.numel(), _stream()), "sanitize")
+    return x
+
+
 def random_permutation(n, device, out=None, seed=None):
     """A pseudo-random permutation of range(n) as an int64 device tensor, without the sort behind
     ``torch.randperm(n, device=...)`` (``wcmc_random_permutation``: keyed Feistel network).  The 62-bit key is drawn

@@ -181,3 +181,269 @@ class FullImageDataset:
             batch, _ = self.batch(k)
             cs = list(zip(*self.coords[k * self.batch_size:(k + 1) * self.batch_size]))
             yield (batch,) + tuple(list(c) for c in cs)
+
+
+# ------------------------------------------------------------------------------------------------- dataset directories
+SHUFFLE_SEED = "Inyoung Cho, Yuchi Huo, Sungeui Yoon @ KAIST"          # datasets.py:270
+TEST_SPPS = (2, 4, 8, 16, 32, 64)                                        # datasets.py:655
+MAX_CONTINUATIONS = 7                                                    # datasets.py:632: <scene>_1.npy .. <scene>_7.npy
+
+
+def shuffled_files(files):
+    """The seeded shuffle of ``gt_files`` (datasets.py:269-271) on a private generator: ``random.seed(s); random.shuffle(x)``
+    without touching the process-wide ``random`` state."""
+    import random
+    files = list(files)
+    random.Random(SHUFFLE_SEED).shuffle(files)
+    return files
+
+
+def grid_origins(h, w, patch_size=PatchBatcher.PATCH_SIZE):
+    """The (row, column) window origins of ``_full_patches`` (datasets.py:842-883), in its order.  Windows that start within
+    ``patch_size`` of the bottom / right edge are ragged in the reference (it crops what is there)."""
+    return np.array([(x, y) for x in range(0, h, patch_size) for y in range(0, w, patch_size)], dtype=np.int32).reshape(-1, 2)
+
+
+def sanitized(a):
+    """Host restatement of the NaN / Inf rule (datasets.py:623-624); ``ops.sanitize_`` is the device kernel."""
+    a = np.asarray(a, dtype=np.float32)
+    a = np.where(np.isfinite(a), a, np.float32(1.0e+38))
+    return np.where(a < np.float32(1.0e+38), a, np.float32(1.0e+38)).astype(np.float32)
+
+
+class _PendingProb:
+    """What ``DenoiseDirectory.reader`` returns for 'prob' while ``_prob_imp.npy`` does not exist: ``staged_hook`` computes the
+    map from the staged frame and writes ``fn``."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+
+class DenoiseDirectory:
+    """The directory and file layer of the reference's ``DenoiseDataset`` (``datasets.py:161-283, 584-715``) for the KPCN base
+    model: renderer output under ``<gt_base_dir>/<mode>/{gt,input}/<scene>.npy`` (gt (H, W, 9), input (H, W, S, 104)).
+
+      * discovery: the ``.npy`` files of ``<mode>/gt`` in sorted order (``os.walk`` lists in the file system's order; sorting
+        makes a run repeatable), then the reference's seeded shuffle (``shuffled_files``);
+      * path rules, as ``FullImageDataset``: ``/gt/`` <-> ``/input/``, and ``/KPCN/`` -> ``/LLPM/`` for the ``_llpm`` files;
+      * no ``get_valid_path`` fallback across mounts: a missing file is a ``FileNotFoundError``;
+      * ``offline_preprocess`` writes what ``_offline_preprocess`` writes, minus the SBMC buffers, computed on the device;
+      * ``reader`` / ``staged_hook`` feed ``support.loader.PatchLoader``; ``origins`` are the grid windows of validation.
+
+    Training runs at the one sample count ``spp``; the reference's ``MSDenoiseDataset`` concatenation over 2..spp is not built.
+    """
+    MAX_DEPTH = DenoisePreprocessor.MAX_DEPTH
+    PATCH_SIZE = PatchBatcher.PATCH_SIZE
+
+    def __init__(self, gt_base_dir, spp, mode='train', batch_size=8, sampling='random', use_llpm_buf=False, device=None,
+                 pnet_out_size=3, patch_size=PATCH_SIZE):
+        import os
+        if mode not in ('train', 'val', 'test'):
+            raise RuntimeError("Unknown training mode %s" % mode)
+        if sampling not in ('random', 'grid'):
+            raise RuntimeError("Unknown sampling mode %s" % sampling)
+        self.gt_dir = os.path.join(gt_base_dir, mode, 'gt')
+        if not os.path.isdir(self.gt_dir):
+            raise FileNotFoundError(self.gt_dir)
+        self.gt_files = shuffled_files(os.path.join(self.gt_dir, f) for f in sorted(os.listdir(self.gt_dir))
+                                       if f.endswith('.npy') and os.path.isfile(os.path.join(self.gt_dir, f)))
+        self.spp, self.batch_size, self.mode, self.sampling = spp, batch_size, mode, sampling
+        self.use_llpm_buf, self.device, self.patch_size = use_llpm_buf, device, patch_size
+        self.pnet_in_size = 36 if use_llpm_buf else 0                    # datasets.py:201-219
+        self.pnet_out_size = pnet_out_size
+        self.dncnn_in_size = 34 + (pnet_out_size + 2 if use_llpm_buf else 0)
+        self.patches_per_image = (256 // batch_size) * batch_size if sampling == 'random' else 100      # datasets.py:273-279
+        self.pre = DenoisePreprocessor(self.MAX_DEPTH)
+
+    def __len__(self):
+        return len(self.gt_files)
+
+    # ---- names
+    def paths(self, i):
+        """The file names that belong to image ``i`` (datasets.py:602-607, :633-634): 'gt', 'in', 'llpm', 'prob', and the
+        functions 'kpcn'(spp), 'in_k'(k), 'llpm_k'(k) of the per-spp and continuation files."""
+        import os
+        gt_fn = self.gt_files[i]
+        in_fn = gt_fn.replace(os.sep + 'gt' + os.sep, os.sep + 'input' + os.sep)
+        stem, ext = in_fn[:in_fn.rfind('.')], in_fn[in_fn.rfind('.'):]
+        to_llpm = lambda fn: fn.replace(os.sep + 'KPCN' + os.sep, os.sep + 'LLPM' + os.sep)      # noqa: E731
+        return {'gt': gt_fn, 'in': in_fn, 'llpm': to_llpm(stem + '_llpm' + ext), 'prob': stem + '_prob_imp' + ext,
+                'kpcn': lambda s: stem + '_kpcn_' + str(s) + ext, 'in_k': lambda k: stem + '_' + str(k) + ext,
+                'llpm_k': lambda k: to_llpm(stem + '_llpm_' + str(k) + ext)}
+
+    @staticmethod
+    def _load(fn, mmap=False):
+        import os
+        if not os.path.isfile(fn):
+            raise FileNotFoundError(fn)
+        return np.load(fn, mmap_mode='r' if mmap else None)
+
+    def _main_raw(self, fn):
+        """The main input file, memory-mapped and cut to ``spp`` samples; a file that holds fewer is an error (the reference
+        would slice what is there and go on at another sample count than asked)."""
+        a = self._load(fn, mmap=True)
+        if a.ndim != 4 or a.shape[-1] != 104:
+            raise ValueError("%s: shape %s is not renderer output (H, W, S, 104)" % (fn, tuple(a.shape)))
+        if a.shape[2] < self.spp:
+            raise ValueError("%s holds %d samples per pixel, fewer than the %d asked for (spp)" % (fn, a.shape[2], self.spp))
+        return a[:, :, :self.spp]
+
+    @staticmethod
+    def _save(fn, arr):
+        """Write through a temporary name: a reader never sees half a file."""
+        import os
+        os.makedirs(os.path.dirname(fn), exist_ok=True)
+        tmp = fn + '.tmp%d' % os.getpid()
+        with open(tmp, 'wb') as f:
+            np.save(f, arr)
+        os.replace(tmp, fn)
+
+    def _device(self):
+        return torch.device(self.device if self.device is not None else torch.cuda.current_device())
+
+    def _upload(self, a):
+        """Host array (a read-only memory map included: it is read into memory first) -> sanitised contiguous fp32 device tensor."""
+        a = np.ascontiguousarray(a, dtype=np.float32) if a.flags.writeable else np.array(a, dtype=np.float32, order='C')
+        return _ops.sanitize_(torch.from_numpy(a).to(self._device()))
+
+    # ---- offline writer
+    def offline_preprocess(self, llpm=True, kpcn=True, overwrite=False, report=None):
+        """``_offline_preprocess`` (datasets.py:584-715) without the SBMC buffers.  Per scene: ``_llpm.npy`` (and ``_llpm_<k>.npy``
+        for the continuation files ``<scene>_<k>.npy`` that exist, k = 1..7), ``_kpcn_<s>.npy`` for s in 2..spp (train / val) or the
+        s of 2, 4, 8, 16, 32, 64 that the samples on disk reach (test), the gt file sanitised, and ``_prob_imp.npy`` outside the
+        test mode.  A file that exists is kept unless ``overwrite``; a scene whose files all exist is not read at all.  Each raw
+        file is uploaded once.  Returns ``[(scene, [files written], seconds)]`` and calls ``report`` with each entry."""
+        import os
+        import time
+        done = []
+        for i in range(len(self.gt_files)):
+            t0 = time.time()
+            p = self.paths(i)
+            written = []
+            if not os.path.isfile(p['in']):
+                raise FileNotFoundError(p['in'])
+            want = lambda fn: overwrite or not os.path.isfile(fn)                                   # noqa: E731
+            conts = []
+            for k in range(1, MAX_CONTINUATIONS + 1):               # a missing continuation file ends the series
+                if not os.path.isfile(p['in_k'](k)):
+                    break
+                conts.append(k)
+            uploaded = {}
+
+            def raw(k):
+                """Sanitised device samples of the main file cut to spp (k = 0) or of continuation file k, uploaded once."""
+                if k not in uploaded:
+                    a = self._main_raw(p['in']) if k == 0 else self._load(p['in_k'](k), mmap=True)
+                    assert a.shape[-1] == 104, 'input numpy file is not produced by OptaGen'
+                    uploaded[k] = self._upload(a)
+                return uploaded[k]
+
+            if llpm:
+                if want(p['llpm']):
+                    self._save(p['llpm'], self.pre._preprocess_llpm(raw(0)).cpu().numpy())
+                    written.append(p['llpm'])
+                for k in conts:
+                    if want(p['llpm_k'](k)):
+                        self._save(p['llpm_k'](k), self.pre._preprocess_llpm(raw(k)).cpu().numpy())
+                        written.append(p['llpm_k'](k))
+            if kpcn:
+                # samples on disk, read once per scene: the main file's first spp (it holds at least spp), then the
+                # continuation files in order
+                counts = {0: self._main_raw(p['in']).shape[2]}
+                counts.update((k, self._load(p['in_k'](k), mmap=True).shape[2]) for k in conts)
+                for s in (TEST_SPPS if self.mode == 'test' else range(2, self.spp + 1)):
+                    parts, have = [0], counts[0]
+                    for k in conts:
+                        if have >= s:
+                            break
+                        parts.append(k)
+                        have += counts[k]
+                    if have < s:
+                        break                                       # (test mode: a missing continuation file ends the series)
+                    if want(p['kpcn'](s)):
+                        x = raw(0) if len(parts) == 1 else torch.cat([raw(k) for k in parts], dim=2)
+                        self._save(p['kpcn'](s), self.pre._preprocess_kpcn(x[:, :, :s].contiguous()).cpu().numpy())
+                        written.append(p['kpcn'](s))
+            # target: rewritten when it is not yet the sanitised fp32 array (the reference rewrites it on every visit)
+            gt = self._load(p['gt'])
+            clean = gt.dtype == np.float32 and bool(np.all(np.isfinite(gt))) and bool(np.all(gt <= np.float32(1.0e+38)))
+            gt_dev = None
+            if overwrite or not clean:
+                gt_dev = self._upload(gt)
+                self._save(p['gt'], gt_dev.cpu().numpy())
+                written.append(p['gt'])
+            if self.mode != 'test' and want(p['prob']):
+                gt_dev = self._upload(gt) if gt_dev is None else gt_dev
+                self._save(p['prob'], _ops.sampling_prob(raw(0), gt_dev, self.patch_size, self.MAX_DEPTH).cpu().numpy())
+                written.append(p['prob'])
+            uploaded.clear()
+            entry = (os.path.basename(p['in'])[:-4], written, time.time() - t0)
+            done.append(entry)
+            if report is not None:
+                report(entry)
+        return done
+
+    # ---- loader side
+    def reader(self, i):
+        """``reader(i)`` of ``support.loader.PatchLoader``: raw memory-mapped and cut to ``[:, :, :spp]``, gt from its file, prob from
+        ``_prob_imp.npy`` -- or, while that file does not exist, a marker that ``staged_hook`` resolves on the device."""
+        import os
+        p = self.paths(i)
+        raw = self._main_raw(p['in'])
+        gt = self._load(p['gt'])
+        prob = _PendingProb(p['prob'])
+        if os.path.isfile(p['prob']):
+            prob = np.load(p['prob'])
+            want = (gt.shape[0] - self.patch_size, gt.shape[1] - self.patch_size)
+            if prob.shape != want:
+                raise ValueError("%s has shape %s; a %d x %d image and patch size %d need %s -- it was written for another patch "
+                                 "size: rewrite it (python -m wcmc_amd.preprocess --patch_size %d --overwrite) or delete it"
+                                 % (p['prob'], tuple(prob.shape), gt.shape[0], gt.shape[1], self.patch_size, want,
+                                    self.patch_size))
+        return {'raw': raw, 'gt': gt, 'prob': prob}
+
+    def staged_hook(self, d_raw, d_gt, prob):
+        """``ImageStager``'s hook on the copy stream, before the preprocessing kernels: the frame is sanitised in place as the
+        offline writer does, and a missing probability map is computed from it and written."""
+        _ops.sanitize_(d_raw)
+        _ops.sanitize_(d_gt)
+        if isinstance(prob, _PendingProb):
+            arr = _ops.sampling_prob(d_raw, d_gt, self.patch_size, self.MAX_DEPTH).cpu().numpy()
+            self._save(prob.fn, arr)
+            prob = arr
+        return prob
+
+    def origins(self, i):
+        """Window origins of image ``i``: the grid of ``_full_patches`` for ``sampling='grid'`` (validation)."""
+        if self.sampling != 'grid':
+            raise RuntimeError("origins(i) is the grid of sampling='grid'; 'random' origins are drawn from the probability map")
+        h, w = self._load(self.gt_files[i], mmap=True).shape[:2]
+        return grid_origins(h, w, self.patch_size)
+
+    def grid_batches(self, indices=None, batch_size=None):
+        """Validation batches: every WHOLE window of the grid (the reference's ragged edge windows cannot be batched), image by
+        image, ``batch_size`` at a time."""
+        bs = self.batch_size if batch_size is None else batch_size
+        batcher = PatchBatcher(self.patch_size, bs)
+        for i in (range(len(self)) if indices is None else indices):
+            item = self.reader(i)
+            d_raw, d_gt = self._upload(item['raw']), self._upload(item['gt'])
+            h, w = d_gt.shape[:2]
+            o = self.origins(i)
+            o = o[(o[:, 0] + self.patch_size <= h) & (o[:, 1] + self.patch_size <= w)]
+            if len(o) == 0:
+                raise ValueError("DenoiseDirectory: the %d x %d image %s holds no whole %d-pixel window"
+                                 % (h, w, self.gt_files[i], self.patch_size))
+            kp = self.pre._preprocess_kpcn(d_raw)
+            ll = self.pre._preprocess_llpm(d_raw) if self.use_llpm_buf else None
+            for k in range(0, len(o), bs):
+                yield batcher.batch(kp, ll, d_gt, o[k:k + bs])
+
+    def num_grid_batches(self, indices=None, batch_size=None):
+        bs = self.batch_size if batch_size is None else batch_size
+        n = 0
+        for i in (range(len(self)) if indices is None else indices):
+            h, w = self._load(self.gt_files[i], mmap=True).shape[:2]
+            o = self.origins(i)
+            n += -(-int(((o[:, 0] + self.patch_size <= h) & (o[:, 1] + self.patch_size <= w)).sum()) // bs)
+        return n

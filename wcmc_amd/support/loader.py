@@ -110,9 +110,13 @@ class ImageStager:
     ``indices``; ``reader(i)`` returns ``{'raw': (H,W,S,C>=104) float32, 'gt': (H,W,9) float32, 'prob': (H,W) | None}`` numpy
     arrays (any object with the buffer protocol that ``torch.from_numpy`` / ``np.asarray`` accepts, e.g. a memmap)."""
 
-    def __init__(self, reader, indices, device, depth=2, use_llpm=True, max_depth=DenoisePreprocessor.MAX_DEPTH, workers=2):
+    def __init__(self, reader, indices, device, depth=2, use_llpm=True, max_depth=DenoisePreprocessor.MAX_DEPTH, workers=2,
+                 staged_hook=None):
         """workers: reader / staging threads (``HostReaderPool``): images i + 1 .. i + workers are read from disk and copied
-        into pinned memory concurrently while image i crosses PCIe."""
+        into pinned memory concurrently while image i crosses PCIe.
+        staged_hook: optional ``hook(d_raw, d_gt, prob) -> prob``, called on the copy stream once the frame is on the device and
+        before the preprocessing kernels (``DenoiseDirectory.staged_hook``: sanitise the frame in place, compute and write a
+        missing probability map).  Without one the staged frame is preprocessed as it is."""
         assert depth >= 2, "double buffering needs two staging slots"
         self.workers = max(1, int(workers))
         self.reader, self.indices, self.device = reader, list(indices), torch.device(device)
@@ -120,6 +124,7 @@ class ImageStager:
             self.device = torch.device(self.device.type, torch.cuda.current_device())
         self.depth, self.use_llpm = depth, use_llpm
         self.pre = DenoisePreprocessor(max_depth)
+        self.staged_hook = staged_hook
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.bytes_moved = 0
 
@@ -152,6 +157,8 @@ class ImageStager:
                 with torch.cuda.stream(self.copy_stream):
                     d_raw = p_raw.to(self.device, non_blocking=True)
                     d_gt = p_gt.to(self.device, non_blocking=True)
+                    if self.staged_hook is not None:
+                        prob = self.staged_hook(d_raw, d_gt, prob)
                     kpcn = self.pre._preprocess_kpcn(d_raw)
                     llpm = self.pre._preprocess_llpm(d_raw) if self.use_llpm else None
                     ev = torch.cuda.Event()
@@ -195,8 +202,9 @@ class PatchLoader:
     """Batches of the KPCN base model over the staged images; ``len()`` = batches per epoch."""
 
     def __init__(self, reader, indices, device, batch_size=8, patch_size=PatchBatcher.PATCH_SIZE, use_llpm=True, depth=2,
-                 patches_per_image=None, prefetch=2, workers=2):
-        self.stager = ImageStager(reader, indices, device, depth=depth, use_llpm=use_llpm, workers=workers)
+                 patches_per_image=None, prefetch=2, workers=2, staged_hook=None):
+        self.stager = ImageStager(reader, indices, device, depth=depth, use_llpm=use_llpm, workers=workers,
+                                  staged_hook=staged_hook)
         self.batcher = PatchBatcher(patch_size, batch_size)
         if patches_per_image is not None:
             self.batcher.patches_per_image = (patches_per_image // batch_size) * batch_size
@@ -237,18 +245,22 @@ class PatchLoader:
                     break
                 kpcn, llpm, gt, prob = got
                 h, w = kpcn.shape[:2]
-                if prob is None:
-                    prob = np.zeros((h, w), dtype=np.float64)         # (not a distribution: uniform, as the reference falls back)
-                # origins must keep the window inside the image: the reference crops what it gets, which silently shrinks a
-                # patch at the border; its probability maps are zero there (datasets.py:795-810)
-                valid = np.zeros((h, w), dtype=np.float64)
-                valid[:h - p + 1, :w - p + 1] = np.asarray(prob, dtype=np.float64)[:h - p + 1, :w - p + 1]
-                s = valid.sum()
-                if s > 0:
-                    valid /= s
+                if prob is not None and np.shape(prob) == (h - p, w - p):
+                    # a map over patch ORIGINS, cropped as `_prob_imp.npy` is (datasets.py:713): the reference's own draw
+                    origins = self.batcher.sample_origins(np.asarray(prob))
                 else:
-                    valid[:h - p + 1, :w - p + 1] = 1.0 / ((h - p + 1) * (w - p + 1))
-                origins = self.batcher.sample_origins(valid)
+                    if prob is None:
+                        prob = np.zeros((h, w), dtype=np.float64)     # (not a distribution: uniform, as the reference falls back)
+                    # origins must keep the window inside the image: the reference crops what it gets, which silently shrinks
+                    # a patch at the border; its probability maps are zero there (datasets.py:795-810)
+                    valid = np.zeros((h, w), dtype=np.float64)
+                    valid[:h - p + 1, :w - p + 1] = np.asarray(prob, dtype=np.float64)[:h - p + 1, :w - p + 1]
+                    s = valid.sum()
+                    if s > 0:
+                        valid /= s
+                    else:
+                        valid[:h - p + 1, :w - p + 1] = 1.0 / ((h - p + 1) * (w - p + 1))
+                    origins = self.batcher.sample_origins(valid)
                 self.batcher.check_origins(origins, h, w)
                 with torch.cuda.stream(side):
                     origins_dev = torch.as_tensor(origins, dtype=torch.int32).to(dev)      # one copy per image

@@ -17,9 +17,10 @@ What differs, on purpose:
     launch with ``python -m torch.distributed.run --nproc-per-node N -m wcmc_amd.train_kpcn ...``; every rank steps on
     its own shard, gradients are summed inside the fused clip + Adam (``wcmc_amd.optim.FusedClipAdam``), rank 0 saves;
   * ``--graph`` replays one hipGraph per step (``wcmc_amd.graph.GraphedTrainStep``) when the loader keeps its shapes;
-  * the reading of the authors' dataset files (``support/datasets.py:MSDenoiseDataset``) is out of scope (SURVEY.md 8,
-    DESIGN.md section 1): ``init_data`` feeds ``--synthetic N`` batches per epoch with the dataset's schema
-    (``wcmc_amd.synthetic``), or any iterable of batch dictionaries handed to ``train`` by the caller;
+  * ``init_data`` feeds ``--synthetic N`` batches per epoch with the dataset's schema (``wcmc_amd.synthetic``) -- the default --
+    or, with ``--from_data_dir``, the renderer output under ``--data_dir`` (``support/datasets.py:DenoiseDirectory`` through
+    ``support/loader.py:PatchLoader``) at the one sample count ``--num_samples``; the reference's ``MSDenoiseDataset``
+    concatenation over 2..spp is not built (INTEGRATION.md section 4).  ``train`` takes any iterable of batch dictionaries;
   * no visdom (``--visual`` is accepted and ignored), no tqdm.
 """
 import argparse
@@ -155,7 +156,43 @@ class SyntheticLoader:
             yield make_batch(b, s, h, seed=self.seed + i, device=self.device, use_llpm=self.use_llpm)
 
 
+class GridValLoader:
+    """``len``-able iterable over the whole grid windows of a ``DenoiseDirectory`` (``sampling='grid'``), ``BS_VAL`` at a time."""
+
+    def __init__(self, directory, indices, batch_size):
+        self.directory, self.indices, self.batch_size = directory, list(indices), batch_size
+
+    def __len__(self):
+        return self.directory.num_grid_batches(self.indices, self.batch_size)
+
+    def __iter__(self):
+        return self.directory.grid_batches(self.indices, self.batch_size)
+
+
+def init_data_dir(args, device, rank=0, world=1):
+    """``--from_data_dir``: ``<data_dir>/train`` through the patch loader, ``<data_dir>/val`` on the grid of ``_full_patches``
+    (``train_kpcn.py:167-189``).  Image indices are strided by rank; every rank gets the same number of images (the ranks step
+    together), so up to ``world - 1`` images at the end of the shuffled list are left out."""
+    from .support.datasets import DenoiseDirectory
+    from .support.loader import PatchLoader
+    kw = dict(use_llpm_buf=args.use_llpm_buf, device=device, patch_size=args.patch_size)
+    tr = DenoiseDirectory(args.data_dir, args.num_samples, 'train', args.batch_size, 'random', **kw)
+    va = DenoiseDirectory(args.data_dir, args.num_samples, 'val', BS_VAL, 'grid', **kw)
+    if len(tr) < world or len(va) < world:
+        raise RuntimeError('%s holds %d training and %d validation images: fewer than the %d ranks'
+                           % (args.data_dir, len(tr), len(va), world))
+    shard = lambda d: range(rank, len(d) // world * world, world)                     # noqa: E731
+    train = PatchLoader(tr.reader, shard(tr), device, batch_size=args.batch_size, patch_size=args.patch_size,
+                        use_llpm=args.use_llpm_buf, patches_per_image=getattr(args, 'patches_per_image', None),
+                        staged_hook=tr.staged_hook)
+    val = GridValLoader(va, shard(va), BS_VAL)
+    sizes = {'dncnn_in_size': tr.dncnn_in_size, 'pnet_in_size': PNET_IN, 'pnet_out_size': tr.pnet_out_size}
+    return sizes, {'train': train, 'val': val}
+
+
 def init_data(args, device, rank=0, world=1):
+    if getattr(args, 'from_data_dir', False):
+        return init_data_dir(args, device, rank, world)
     n = max(1, args.synthetic)
     train = SyntheticLoader(n, args.batch_size, args.patch_size, 8, args.use_llpm_buf, 1000 * (rank + 1), device)
     val = SyntheticLoader(max(1, n // 4), BS_VAL, args.patch_size, 8, args.use_llpm_buf, 7_000_000 + 1000 * rank, device)
@@ -256,7 +293,7 @@ def build_parser():
     p.add_argument('--sbmc', action='store_true')
     p.add_argument('--p_buf', action='store_true')
     p.add_argument('--model_name', type=str, default='tSUNet', help='name of the model.')
-    p.add_argument('--data_dir', type=str, default='./data', help='directory of dataset (unused: see --synthetic)')
+    p.add_argument('--data_dir', type=str, default='./data', help='directory of dataset: <data_dir>/{train,val}/{gt,input}/<scene>.npy (read with --from_data_dir)')
     p.add_argument('--visual', action='store_true', help='accepted for compatibility; there is no visdom here')
     p.add_argument('-b', '--batch_size', type=int, default=64, help='batch size (per GPU).')
     p.add_argument('-e', '--num_epoch', type=int, default=100, help='number of epochs.')
@@ -287,8 +324,14 @@ def build_parser():
     p.add_argument('--not_save', action='store_true', help='do not save checkpoint (debugging purpose).')
     p.add_argument('--local', action='store_true')
     # this build
-    p.add_argument('--synthetic', type=int, default=16, help='synthetic batches per epoch (the dataset reader is out of scope)')
+    p.add_argument('--synthetic', type=int, default=16, help='synthetic batches per epoch (without --from_data_dir)')
     p.add_argument('--patch_size', type=int, default=128)
+    p.add_argument('--from_data_dir', action='store_true',
+                   help='train on <data_dir>/train and validate on <data_dir>/val at --num_samples samples per pixel '
+                        '(python -m wcmc_amd.preprocess writes the probability maps ahead of time; a missing one is computed '
+                        'on the device and written)')
+    p.add_argument('--patches_per_image', type=int, default=None,
+                   help='with --from_data_dir: patches drawn per image and epoch (default: (256 // batch_size) * batch_size)')
     p.add_argument('--graph', action='store_true', help='one hipGraph replay per training step')
     p.add_argument('--defer_check', dest='defer_check', action='store_true', default=True,
                    help="with --graph (the default there): check a step's losses for non-finite values after the NEXT step has "
