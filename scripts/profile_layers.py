@@ -33,7 +33,7 @@ class Proxy:
             return wrapped
         return fn
 
-ops.lib = lambda: Proxy()
+ops.conv_split.lib = lambda: Proxy()        # (the module that launches the two wrapped entries looks `lib` up in its own namespace)
 itf = bench.build_interface(dev, None)
 batch = make_batch(8, 8, 128, seed=0, device=dev)
 for it in range(3):

@@ -117,6 +117,40 @@ def test_ops_fail_loudly_without_gpu():
         GlobalRelativeSimilarityLoss()(torch.zeros(1, 2, 3, 4, 4), torch.zeros(1, 3, 4, 4))
 
 
+def test_ops_switches_have_one_home_that_every_module_reads():
+    """``wcmc_amd.ops`` is configured by assignment from outside (bench.py, graph.py, conftest.py, scripts/): every such name is
+    bound in the package alone, and the modules see an assignment at their next call."""
+    import importlib
+    import pkgutil
+    from wcmc_amd import ops
+    switches = ("PRECISION", "USE_SIDE_STREAM", "USE_BRANCH_STREAM", "FUSE_EMBED", "FUSE_FINAL", "TERMS_BY_KS", "EMULATE_HIDDEN",
+                "DEBUG_ACTS", "DEFER_MAX_BYTES", "_PROFILER", "_DEFERRED")
+    mods = [importlib.import_module("wcmc_amd.ops." + m.name) for m in pkgutil.iter_modules(ops.__path__)]
+    assert len(mods) >= 11, [m.__name__ for m in mods]
+    for m in mods:
+        assert getattr(m, "_sw", ops) is ops
+        for name in switches:
+            assert hasattr(ops, name) and not hasattr(m, name), "%s holds a binding of %s of its own" % (m.__name__, name)
+    old = ops.PRECISION
+    try:
+        ops.set_precision("bf16x321")
+        assert ops.split_path() is True and ops.conv_split._sw.PRECISION == "bf16x321" and ops.conv_split._dgrad_mode() == 2
+        ops.set_precision("fp32")
+        assert ops.split_path() is False and ops.conv_split._sw.PRECISION == "fp32" and ops.conv_split._dgrad_mode() == 1
+    finally:
+        ops.set_precision(old)
+    side = ops.USE_SIDE_STREAM
+    try:
+        dev = torch.device("cuda", 0)
+        if torch.cuda.is_available():               # (a stream needs the device; the switch's off position does not)
+            ops.USE_SIDE_STREAM = True
+            assert isinstance(ops.streams._side_stream(dev), torch.cuda.Stream)
+        ops.USE_SIDE_STREAM = False
+        assert ops.streams._side_stream(dev) is None
+    finally:
+        ops.USE_SIDE_STREAM = side
+
+
 def test_product_never_imports_oracle():
     import subprocess
     out = subprocess.run(["grep", "-rn", "-E", r"^\s*(from|import)\s+oracle", os.path.join(ROOT, "wcmc_amd")],

@@ -1,0 +1,210 @@
+"""The data step on the device: preprocessing and patch assembly (csrc/preprocess.hip), the sampling maps (csrc/sampling_map.hip),
+permutations, and the tile stitching of full-frame inference."""
+import ctypes
+import math
+
+import torch
+
+from .._lib import check, lib
+from ._base import _need_cuda, _ptr, _stream
+
+
+# ---------------------------------------------------------------------------------- data step
+def _need_dense(t, ndim):
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != ndim or not t.is_contiguous():
+        raise RuntimeError("wcmc_amd preprocessing takes contiguous fp32 CUDA tensors in the reference's numpy "
+                           "layout (got %s %s %s); there is no CPU path" % (t.device, t.dtype, tuple(t.shape)))
+
+
+def preprocess_llpm(sample, max_depth=5):
+    """``DenoiseDataset._preprocess_llpm`` (datasets.py:302-361): raw (h,w,s,C) -> (h,w,s,37)."""
+    _need_dense(sample, 4)
+    h, w, s, c = sample.shape
+    out = torch.empty((h, w, s, 7 + 5 * (max_depth + 1)), device=sample.device, dtype=torch.float32)
+    check(lib().wcmc_preprocess_llpm(_ptr(sample), h * w * s, c, max_depth, _ptr(out), _stream()), "preprocess_llpm")
+    return out
+
+
+def preprocess_kpcn(sample, max_depth=5):
+    """``DenoiseDataset._preprocess_kpcn`` (datasets.py:487-582): raw (h,w,s,C) -> (h,w,44)."""
+    _need_dense(sample, 4)
+    h, w, s, c = sample.shape
+    out = torch.empty((h, w, 44), device=sample.device, dtype=torch.float32)
+    nbytes = lib().wcmc_preprocess_kpcn_workspace_bytes(h, w)
+    ws = torch.empty((nbytes + 3) // 4, device=sample.device, dtype=torch.float32)
+    check(lib().wcmc_preprocess_kpcn(_ptr(sample), h, w, s, c, max_depth, _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
+          "preprocess_kpcn")
+    return out
+
+
+def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch):
+    """The batch dictionary of the KPCN base model for windows of `patch` pixels at `origins` ((B, 2) int32 device
+    tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device)."""
+    _need_cuda(kpcn, gt)
+    if not origins.is_cuda:
+        raise RuntimeError("assemble_kpcn_patches: origins must be a device tensor")
+    h, w = kpcn.shape[:2]
+    assert kpcn.shape == (h, w, 44) and gt.shape == (h, w, 9) and kpcn.is_contiguous() and gt.is_contiguous()
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
+    b, s = origins.shape[0], 0
+    if llpm is not None:
+        assert llpm.shape[:2] == (h, w) and llpm.shape[3] == 37 and llpm.is_contiguous()
+        s = llpm.shape[2]
+    dev = kpcn.device
+    cin = 35 if llpm is not None else 34
+    shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
+              "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
+              "kpcn_albedo": (b, 3, patch, patch), "target_diffuse": (b, 3, patch, patch),
+              "target_specular": (b, 3, patch, patch), "target_total": (b, 3, patch, patch)}
+    if llpm is not None:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    # ONE allocation, the entries are views of it: a consumer on another stream keeps the batch alive with one
+    # `record_stream` and frees one block (nine of each cost the training thread 0.25 ms per step: scripts/diag_loader_gap.py)
+    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}          # (every entry starts on a 256-byte boundary)
+    flat = torch.empty(sum(sizes.values()), device=dev, dtype=torch.float32)
+    out, off = {}, 0
+    for k, shp in shapes.items():
+        out[k] = flat[off:off + math.prod(shp)].view(shp)
+        off += sizes[k]
+    check(lib().wcmc_assemble_kpcn_patches(_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w,
+                                           s, patch, _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
+                                           _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
+                                           _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
+                                           _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream()),
+          "assemble_kpcn_patches")
+    return out
+
+
+def gradients(buf):
+    """``DenoiseDataset._gradients`` (datasets.py:286-300): (h,w,c) -> (h,w,2c)."""
+    _need_dense(buf, 3)
+    h, w, c = buf.shape
+    out = torch.empty((h, w, 2 * c), device=buf.device, dtype=torch.float32)
+    check(lib().wcmc_gradients(_ptr(buf), h, w, c, _ptr(out), _stream()), "gradients")
+    return out
+
+
+def reflect_index(i, n):
+    """Source index of position ``i`` of a line of ``n`` entries under scipy's 'reflect' boundary (``wcmc_reflect_index``: the
+    map the Gaussian passes of ``importance_map`` use; no GPU call)."""
+    return int(lib().wcmc_reflect_index(int(i), int(n)))
+
+
+def importance_map(img):
+    """``gradient_importance_map`` (datasets.py:17-36): (H, W) or (H, W, 3) -> (H, W) in [0, 1]."""
+    if img.dim() == 2:
+        h, w, c = img.shape[0], img.shape[1], 1
+    elif img.dim() == 3 and img.shape[2] in (1, 3):
+        h, w, c = img.shape
+    else:
+        raise ValueError("importance_map: the image should be (H, W) or (H, W, 3), got %s" % (tuple(img.shape),))
+    _need_dense(img, img.dim())
+    out = torch.empty((h, w), device=img.device, dtype=torch.float32)
+    nbytes = lib().wcmc_importance_map_workspace_bytes(h, w, c)
+    ws = torch.empty((nbytes + 3) // 4, device=img.device, dtype=torch.float32)
+    check(lib().wcmc_importance_map(_ptr(img), h, w, c, _ptr(out), _ptr(ws), ws.numel() * 4, _stream()), "importance_map")
+    return out
+
+
+def sampling_prob(raw, gt, patch_size=128, max_depth=5):
+    """The patch-sampling map of ``_offline_preprocess`` (datasets.py:697-715): sanitised raw (H, W, S, 104) and gt (H, W, 9)
+    -> (H - patch_size, W - patch_size), a distribution over patch origins."""
+    _need_dense(raw, 4)
+    _need_dense(gt, 3)
+    h, w, s, c = raw.shape
+    if tuple(gt.shape) != (h, w, 9):
+        raise ValueError("sampling_prob: gt should be (%d, %d, 9), got %s" % (h, w, tuple(gt.shape)))
+    if h <= patch_size or w <= patch_size:
+        raise ValueError("sampling_prob: the image (%d x %d) must be larger than the patch (%d) in both dimensions"
+                         % (h, w, patch_size))
+    out = torch.empty((h - patch_size, w - patch_size), device=raw.device, dtype=torch.float32)
+    nbytes = lib().wcmc_sampling_prob_workspace_bytes(h, w, patch_size)
+    ws = torch.empty((nbytes + 7) // 8, device=raw.device, dtype=torch.float64)
+    check(lib().wcmc_sampling_prob(_ptr(raw), _ptr(gt), h, w, s, c, max_depth, patch_size, _ptr(out), _ptr(ws), ws.numel() * 8,
+                                   _stream()), "sampling_prob")
+    return out
+
+
+def sanitize_(x):
+    """NaN / Inf / >= 1e38 -> 1e38 in place (datasets.py:623-624)."""
+    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("sanitize_ takes a contiguous fp32 CUDA tensor (got %s %s); there is no CPU path" % (x.device, x.dtype))
+    check(lib().wcmc_sanitize(_ptr(x), x.numel(), _stream()), "sanitize")
+    return x
+
+
+def random_permutation(n, device, out=None, seed=None):
+    """A pseudo-random permutation of range(n) as an int64 device tensor, without the sort behind
+    ``torch.randperm(n, device=...)`` (``wcmc_random_permutation``: keyed Feistel network).  The 62-bit key is drawn
+    from torch's default CPU generator, so ``torch.manual_seed`` fixes the sequence of permutations."""
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.numel() == n and out.is_contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    check(lib().wcmc_random_permutation(_ptr(out), n, int(seed), _stream()), "random_permutation")
+    return out
+
+
+def random_permutation_dev(out, state, slot):
+    """``random_permutation`` keyed from the device tensor ``state`` = [seed, step counter] (int64) and ``slot``: the form a hipGraph
+    can replay with another key every step (``wcmc_random_permutation_dev``)."""
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and state.is_cuda and state.dtype == torch.int64 and state.numel() >= 2
+    check(lib().wcmc_random_permutation_dev(_ptr(out), out.numel(), _ptr(state), int(slot), _stream()), "random_permutation_dev")
+    return out
+
+
+def step_counter_advance(state):
+    """state[1] += 1 on the device (``wcmc_step_counter_advance``)."""
+    check(lib().wcmc_step_counter_advance(_ptr(state), _stream()), "step_counter_advance")
+
+
+def permutation_key(seed, counter, slot):
+    """Host mirror of the key ``random_permutation_dev`` forms (``wcmc_permutation_key``; no GPU call)."""
+    return int(lib().wcmc_permutation_key(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), int(slot)))
+
+
+def check_tile_coords(coords, h, w, patch):
+    """Host check of a (B, 6) tile table (i_start, j_start, i_end, j_end, i, j) before it goes to ``stitch_tiles``: every owned
+    window lies inside the frame and inside its tile."""
+    for i0, j0, i1, j1, i, j in coords:
+        if not (0 <= i0 < i1 <= h and 0 <= j0 < j1 <= w and i <= i0 and j <= j0 and i1 <= i + patch and j1 <= j + patch):
+            raise ValueError("stitch_tiles: tile %s does not fit a %d x %d frame of %d-pixel tiles"
+                             % ((i0, j0, i1, j1, i, j), h, w, patch))
+
+
+def stitch_tiles(out, p_buffers, coords, out_rad, out_path=None, patch=128):
+    """Paste one batch of tiles into the full frame (``wcmc_stitch_tiles``; the slice loop of test_models.py:75-89).
+    out: (B, 3, ho, wo) network output ('replicate'-padded back to ``patch`` on the fly when smaller); p_buffers: None, a
+    (B, S, C, patch, patch) tensor or a dict of them; coords: device int32 (B, 6) table whose rows passed
+    ``check_tile_coords``; out_rad (3, H, W) and out_path ((S, C, H, W), or a dict of them keyed like p_buffers) are written
+    in place.  Bit-identical to the slice copies."""
+    _need_cuda(out, out_rad)
+    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
+            and coords.is_contiguous()):
+        raise RuntimeError("stitch_tiles: coords must be a contiguous device int32 (B, 6) tensor")
+    b, c3, ho, wo = out.shape
+    _, h, w = out_rad.shape
+    assert c3 == 3 and coords.shape[0] == b and out_rad.shape[0] == 3 and out_rad.is_contiguous()
+    pairs = []
+    if p_buffers is not None:
+        if isinstance(p_buffers, dict):
+            pairs = [(p_buffers[k], out_path[k]) for k in p_buffers]
+        else:
+            pairs = [(p_buffers, out_path)]
+    for pb, op in pairs:
+        _need_cuda(pb, op)
+        assert pb.dim() == 5 and pb.shape[0] == b and tuple(pb.shape[3:]) == (patch, patch) and pb.is_contiguous()
+        assert tuple(op.shape) == (pb.shape[1], pb.shape[2], h, w) and op.is_contiguous()
+    # two P-buffers of one shape per launch; anything else in further launches (the radiance is re-copied: same values)
+    groups = [pairs[i:i + 2] for i in range(0, len(pairs), 2)] or [[]]
+    if len(pairs) == 2 and pairs[0][0].shape != pairs[1][0].shape:
+        groups = [[pairs[0]], [pairs[1]]]
+    for g in groups:
+        pa, oa = g[0] if len(g) > 0 else (None, None)
+        pbb, ob = g[1] if len(g) > 1 else (None, None)
+        s, c = (pa.shape[1], pa.shape[2]) if pa is not None else (0, 0)
+        check(lib().wcmc_stitch_tiles(_ptr(out), *out.stride(), ho, wo, _ptr(pa), _ptr(pbb), s, c, patch,
+                                      ctypes.c_void_p(coords.data_ptr()), b, h, w, _ptr(out_rad), _ptr(oa), _ptr(ob),
+                                      _stream()), "stitch_tiles")
+    return out_rad, out_path
