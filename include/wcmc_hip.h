@@ -567,6 +567,33 @@ int wcmc_sampling_prob(const float* raw, const float* gt, int H, int W, int S, i
                        void* workspace, size_t workspace_bytes, void* stream);
 int wcmc_sanitize(float* x, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------- the data step of the sample-based denoisers (csrc/sbmc_data.hip)
+ * wcmc_preprocess_sbmc: DenoiseDataset._preprocess_sbmc (support/datasets.py:363-485; channel order and arithmetic :394-452).
+ *   raw (h, w, s, C >= 38 + 11*(max_depth+1)), sanitised -> out_s (h, w, s, 27) and out_p (h, w, s, 11*(max_depth+1)) = 66:
+ *   out_s = [max(total, 0) (3), log(1 + max(total, 0)) / 10 (3), log(1 + max(max(total, 0) - max(diffuse, 0), 0)) / 10 (3),
+ *            subpixel = raw 0:2, raw 8:24 verbatim (albedo / normal at first and at first non-specular bounce, depths, visibility, hasHit)]
+ *   out_p = [log(max(prob, 0) + 1e-5) / 30 (4d), clip(light_directions, -1, 1) (2d), then the five tag planes of bits 0..4 of the
+ *            bounce type, plane-major: is_reflection x d, is_transmission x d, is_diffuse x d, is_glossy x d, is_specular x d]
+ *   The bounce code is the float truncated toward zero, as astype(np.int16) does for a value that int16 holds; a code outside
+ *   [-32768, 32767] -- the 1e38 that sanitising leaves -- gives all five flags 0 (numpy's result for such a cast is whatever the
+ *   host's conversion instruction leaves: undefined in C).
+ *   tiled: -1 picks the form (LDS-staged for 16-byte aligned records, else one thread per element), 0 / 1 force the generic / the
+ *   tiled form (1 is an error where the tiled form does not apply); the two forms are bit-identical.
+ * wcmc_assemble_sample_patches: the sample-based batch of DenoiseDataset.__getitem__ (:1045-1073, 1086-1118) after _transpose
+ *   (:760-791), for B windows of P x P pixels at origins[b] = (row, column) (device int32 [B][2], windows in bounds) of one image:
+ *   sbmc_s (H, W, S, 27), sbmc_p (H, W, S, 66; may be null without use_sbmc_buf), llpm (H, W, S, 37) or null, gt (H, W, 9) ->
+ *     radiance (B, S, 3, P, P) = sbmc_s 0:3
+ *     features (B, S, F, P, P) = [sbmc_s 3:27 if use_g_buf else sbmc_s 3:6] ++ [sbmc_p if use_sbmc_buf] ++ [llpm 0:1 if llpm]
+ *                                F = 24 | 3, + 66, + 1
+ *     paths    (B, S, 36, P, P) = llpm 1:37 (only with llpm)
+ *     target_image (B, 3, P, P) = gt 0:3
+ *   One launch; copies only (bit-exact). */
+int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples /* h*w*s */, int C, int max_depth, float* out_s, float* out_p,
+                         int tiled, void* stream);
+int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
+                                 const int* origins, int B, int H, int W, int S, int P, int use_g_buf, int use_sbmc_buf,
+                                 float* radiance, float* features, float* paths, float* target_image, void* stream);
+
 /* ---------------------------------------------------------------- full-frame evaluation
  * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
  * (scene, spp) cell.  out / ipt / tgt: fp32 (H, W, 3) images, element (y, x, c) at p[y*sh + x*sw + c*sc] (any int64

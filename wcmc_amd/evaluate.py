@@ -36,7 +36,8 @@ def load_input(filename, spp, args, device=None):
     if 'KPCN' in args.model_name:
         return FullImageDataset(filename, spp, 'kpcn', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf,
                                 args.pnet_out_size[0], device=device)
-    raise NotImplementedError("evaluate: only KPCN models are evaluated (SBMC / LBMC base denoisers are stand-ins here)")
+    raise NotImplementedError("evaluate: only KPCN models are evaluated; an SBMC / LBMC model needs a base denoiser that the caller must supply "
+                              "(support.datasets.SampleFullImageDataset yields its tiles)")
 
 
 def _model_path(args):
@@ -52,7 +53,8 @@ def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,
     assert os.path.isdir(input_dir), input_dir
     assert 'KPCN' in args.model_name or 'BMC' in args.model_name, args.model_name
     if 'KPCN' not in args.model_name:
-        raise NotImplementedError("evaluate: only KPCN models are evaluated (SBMC / LBMC base denoisers are stand-ins here)")
+        raise NotImplementedError("evaluate: only KPCN models are evaluated; an SBMC / LBMC model needs a base denoiser that the caller must supply "
+                              "(support.datasets.SampleFullImageDataset yields its tiles)")
     device = torch.device(device if device is not None else torch.cuda.current_device())
     spps = list(spps)
     if scenes is None:

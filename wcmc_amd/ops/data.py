@@ -1,5 +1,6 @@
 """The data step on the device: preprocessing and patch assembly (csrc/preprocess.hip), the sampling maps (csrc/sampling_map.hip),
-permutations, and the tile stitching of full-frame inference."""
+the buffers and batches of the sample-based denoisers (csrc/sbmc_data.hip), permutations, and the tile stitching of full-frame
+inference."""
 import ctypes
 import math
 
@@ -72,6 +73,79 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch):
                                            _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
                                            _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream()),
           "assemble_kpcn_patches")
+    return out
+
+
+def preprocess_sbmc(sample, max_depth=5, tiled=None):
+    """``DenoiseDataset._preprocess_sbmc`` (datasets.py:363-485): sanitised raw (h,w,s,C) -> (sbmc_s (h,w,s,27), sbmc_p (h,w,s,66)).
+    ``tiled``: None lets the library pick the form, False / True force the one-thread-per-element / the LDS-staged form (which
+    refuses records that are not 16-byte aligned); the two are bit-identical."""
+    _need_dense(sample, 4)
+    h, w, s, c = sample.shape
+    out_s = torch.empty((h, w, s, 27), device=sample.device, dtype=torch.float32)
+    out_p = torch.empty((h, w, s, 11 * (max_depth + 1)), device=sample.device, dtype=torch.float32)
+    check(lib().wcmc_preprocess_sbmc(_ptr(sample), h * w * s, c, max_depth, _ptr(out_s), _ptr(out_p),
+                                     -1 if tiled is None else int(bool(tiled)), _stream()), "preprocess_sbmc")
+    return out_s, out_p
+
+
+def check_patch_origins(origins, h, w, patch, who="assemble_sample_patches"):
+    """Host check of (B, 2) window origins (rows, columns): every ``patch``-pixel window lies inside the h x w image."""
+    import numpy as np
+    o = origins.cpu().numpy() if isinstance(origins, torch.Tensor) else np.asarray(origins)
+    if o.size and (int(o[:, 0].max()) + patch > h or int(o[:, 1].max()) + patch > w or int(o.min()) < 0):
+        raise ValueError("%s: a %d-pixel patch origin lies outside the %dx%d image" % (who, patch, h, w))
+
+
+def sample_feature_size(use_g_buf=True, use_sbmc_buf=True, use_llpm_buf=False):
+    """Channels of the ``features`` entry of a sample-based batch (datasets.py:1058-1073, 1094-1098): 90 / 24 / 69 / 3, + 1."""
+    return (24 if use_g_buf else 3) + (66 if use_sbmc_buf else 0) + (1 if use_llpm_buf else 0)
+
+
+def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True):
+    """The batch dictionary of the SBMC / LBMC interfaces (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and
+    ``target_image``) for windows of ``patch`` pixels at ``origins`` ((B, 2) int32 (row, column); numpy or tensor) of one image's
+    buffers (datasets.py:1045-1073, 1086-1118 and ``_transpose`` on the device, one launch).  ``sbmc_p`` may be None without
+    ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  ``check_origins=False``: the caller has checked them
+    on the host (checking a device tensor here synchronises)."""
+    _need_cuda(sbmc_s, gt)
+    h, w, s = sbmc_s.shape[:3]
+    if tuple(sbmc_s.shape) != (h, w, s, 27) or tuple(gt.shape) != (h, w, 9) or not (sbmc_s.is_contiguous() and gt.is_contiguous()):
+        raise ValueError("assemble_sample_patches: sbmc_s should be contiguous (H, W, S, 27) and gt (H, W, 9), got %s and %s"
+                         % (tuple(sbmc_s.shape), tuple(gt.shape)))
+    if use_sbmc_buf:
+        _need_cuda(sbmc_p)
+    for name, t, c in (("sbmc_p", sbmc_p if use_sbmc_buf else None, 66), ("llpm", llpm, 37)):
+        if t is not None and (tuple(t.shape) != (h, w, s, c) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError("assemble_sample_patches: %s should be a contiguous fp32 (%d, %d, %d, %d) device tensor, got %s"
+                             % (name, h, w, s, c, tuple(t.shape)))
+    if patch < 1 or patch > h or patch > w:
+        raise ValueError("assemble_sample_patches: a %d-pixel patch does not fit the %dx%d image" % (patch, h, w))
+    if check_origins:
+        check_patch_origins(origins, h, w, patch)
+    if not isinstance(origins, torch.Tensor):
+        import numpy as np
+        origins = torch.as_tensor(np.asarray(origins), dtype=torch.int32)
+    origins = origins.to(sbmc_s.device, torch.int32).contiguous()
+    assert origins.dim() == 2 and origins.shape[1] == 2
+    b = origins.shape[0]
+    f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
+    shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
+    if llpm is not None:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    shapes["target_image"] = (b, 3, patch, patch)
+    # ONE allocation, the entries are views of it (as assemble_kpcn_patches)
+    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
+    flat = torch.empty(sum(sizes.values()), device=sbmc_s.device, dtype=torch.float32)
+    out, off = {}, 0
+    for k, shp in shapes.items():
+        out[k] = flat[off:off + math.prod(shp)].view(shp)
+        off += sizes[k]
+    check(lib().wcmc_assemble_sample_patches(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt),
+                                             ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, int(bool(use_g_buf)),
+                                             int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
+                                             _ptr(out.get("paths")), _ptr(out["target_image"]), _stream()),
+          "assemble_sample_patches")
     return out
 
 

@@ -33,6 +33,49 @@ class DenoisePreprocessor:
         gradients (datasets.py:487-582)."""
         return _ops.preprocess_kpcn(sample, self.max_depth)
 
+    def _preprocess_sbmc(self, sample):
+        """sanitised raw (h, w, s, 104) -> (sbmc_s (h, w, s, 27), sbmc_p (h, w, s, 66)): per-sample radiance, log radiance, log
+        specular, subpixel and g-buffer; log sampling probabilities, clipped light directions and the five planes of
+        light-material interaction tags (datasets.py:363-485)."""
+        return _ops.preprocess_sbmc(sample, self.max_depth)
+
+
+def sample_flags(base_model, use_g_buf=True, use_sbmc_buf=True):
+    """(base_model, use_g_buf, use_sbmc_buf) as ``DenoiseDataset.__init__`` resolves them (datasets.py:171-174, 198-199): 'lbmc' is
+    'sbmc' with the g-buffer and without the SBMC buffers; only 'sbmc' reads the SBMC buffers."""
+    if base_model not in ('kpcn', 'sbmc', 'lbmc'):
+        raise RuntimeError("Unknown baseline model %s" % base_model)
+    if base_model == 'lbmc':
+        base_model, use_sbmc_buf, use_g_buf = 'sbmc', False, True
+    if base_model != 'sbmc':
+        use_sbmc_buf = False
+    return base_model, bool(use_g_buf), bool(use_sbmc_buf)
+
+
+def dncnn_in_size(base_model, use_g_buf, use_sbmc_buf, use_llpm_buf, pnet_out_size):
+    """datasets.py:208-219, on flags already resolved by ``sample_flags``."""
+    n = 34 if base_model == 'kpcn' else 3 + (21 if use_g_buf else 0) + (66 if use_sbmc_buf else 0)
+    return n + (pnet_out_size + 2 if use_llpm_buf else 0)          # path weight, p-buffer, variance
+
+
+class SamplePatchBatcher:
+    """``PatchBatcher`` for the sample-based base models: the dictionary ``SBMCInterface`` / ``LBMCInterface`` assert on
+    (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and ``target_image``; datasets.py:1045-1073, 1086-1118) in one launch
+    of ``ops.assemble_sample_patches``."""
+
+    def __init__(self, patch_size=128, batch_size=8, use_g_buf=True, use_sbmc_buf=True):
+        self.patch_size, self.use_g_buf, self.use_sbmc_buf = patch_size, use_g_buf, use_sbmc_buf
+        self.patches_per_image = (256 // batch_size) * batch_size          # datasets.py:275
+
+    sample_origins = None                               # (bound below to PatchBatcher's: the same draw)
+
+    def check_origins(self, origins, h, w):
+        _ops.check_patch_origins(origins, h, w, self.patch_size, who="SamplePatchBatcher")
+
+    def batch(self, sbmc_s, sbmc_p, llpm, gt, origins, check=True):
+        return _ops.assemble_sample_patches(sbmc_s, sbmc_p if self.use_sbmc_buf else None, llpm, gt, origins, self.patch_size,
+                                            self.use_g_buf, self.use_sbmc_buf, check_origins=check)
+
 
 class PatchBatcher:
     """KPCN-base-model batches straight from one image's device-resident buffers.
@@ -74,9 +117,14 @@ class PatchBatcher:
         return _ops.assemble_kpcn_patches(kpcn, llpm, gt, o.to(kpcn.device, torch.int32).contiguous(), self.patch_size)
 
 
+SamplePatchBatcher.sample_origins = PatchBatcher.sample_origins
+
+
 class FullImageDataset:
-    """Device-side counterpart of the reference's ``FullImageDataset`` (``datasets.py:1174-1424``) for the KPCN base model: the
-    tiles of one full frame for evaluation (``test_models.py``), assembled on the GPU from the offline-preprocessed files.
+    """Device-side counterpart of the reference's ``FullImageDataset`` (``datasets.py:1174-1424``): the tiles of one full frame
+    for evaluation (``test_models.py``), assembled on the GPU from the offline-preprocessed files.  With ``base_model`` 'sbmc' /
+    'lbmc' the files are ``<scene>_sbmc_s.npy`` / ``_sbmc_p.npy`` (``/KPCN/`` -> ``/SBMC/``; continuation files as for ``_llpm``,
+    :1323-1351) and the tiles are the sample-based dictionary of ``ops.assemble_sample_patches``; for 'kpcn':
 
     ``in_fn`` is ``.../input/<scene>.npy``; the files read are those of ``_load_full_buffer`` (:1319-1416):
       * ``<scene>_kpcn_<spp>.npy``  (H, W, 44) KPCN buffers;
@@ -97,16 +145,18 @@ class FullImageDataset:
     MAX_DEPTH = 5
     PATCH_SIZE = 128
     PAD_SIZE = 32
+    SAMPLE_BASED = False                               # SampleFullImageDataset: accepts 'sbmc' / 'lbmc'
 
     def __init__(self, in_fn, spp, base_model='kpcn', use_g_buf=True, use_sbmc_buf=True, use_llpm_buf=False,
                  pnet_out_size=3, device=None, batch_size=None):
         import os
         from .inference import tile_coords
-        if base_model not in (self.KPCN, self.SBMC, self.LBMC):
-            raise RuntimeError("Unknown baseline model %s" % base_model)
-        if base_model != self.KPCN:
-            raise NotImplementedError("FullImageDataset: only the KPCN base model is evaluated here (the SBMC / LBMC base "
-                                      "denoisers are stand-ins in this build)")
+        asked = base_model
+        base_model, use_g_buf, use_sbmc_buf = sample_flags(base_model, use_g_buf, use_sbmc_buf)      # datasets.py:1193-1196
+        if asked != self.KPCN and not self.SAMPLE_BASED:
+            raise NotImplementedError("FullImageDataset: only the KPCN base model is evaluated here; SampleFullImageDataset "
+                                      "yields the tiles of the sample-based models ('sbmc' / 'lbmc'), whose base denoiser the "
+                                      "caller supplies")
         assert os.sep + 'input' + os.sep in in_fn, in_fn
         if batch_size is None:
             if spp <= 32:
@@ -121,31 +171,44 @@ class FullImageDataset:
         self.use_g_buf, self.use_sbmc_buf, self.use_llpm_buf = use_g_buf, use_sbmc_buf, use_llpm_buf
         self.pnet_in_size = 36 if use_llpm_buf else 0
         self.pnet_out_size = pnet_out_size
-        self.dncnn_in_size = 34 + (pnet_out_size + 2 if use_llpm_buf else 0)
+        self.dncnn_in_size = dncnn_in_size(base_model, use_g_buf, use_sbmc_buf, use_llpm_buf, pnet_out_size)
 
         stem, ext = in_fn[:in_fn.rfind('.')], in_fn[in_fn.rfind('.'):]
-        kpcn_fn = stem + '_kpcn_' + str(spp) + ext
         llpm_fn = (stem + '_llpm' + ext).replace(os.sep + 'KPCN' + os.sep, os.sep + 'LLPM' + os.sep)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)   # noqa: E731
-        self.kpcn = up(self._load(kpcn_fn))
+
+        def all_spp(fn, first=None):
+            """``_load_all_spp_buffer`` (:1302-1317): ``fn``, then ``fn`` with _1, _2, ... until ``spp`` samples are there."""
+            parts = [up(self._load(fn)) if first is None else first]
+            n, i = parts[0].shape[2], 0
+            while n < spp:
+                i += 1
+                parts.append(up(self._load(fn[:-4] + '_' + str(i) + '.npy')))
+                n += parts[-1].shape[2]
+            return (torch.cat(parts, dim=2) if len(parts) > 1 else parts[0])[:, :, :spp].contiguous()
+
+        self.kpcn = self.sbmc_s = self.sbmc_p = None
+        if base_model == self.KPCN:
+            self.kpcn = up(self._load(stem + '_kpcn_' + str(spp) + ext))
+        else:                                                    # datasets.py:1323-1351
+            to_sbmc = lambda fn: fn.replace(os.sep + 'KPCN' + os.sep, os.sep + 'SBMC' + os.sep)      # noqa: E731
+            self.sbmc_s = all_spp(to_sbmc(stem + '_sbmc_s' + ext))
+            if use_sbmc_buf:
+                self.sbmc_p = all_spp(to_sbmc(stem + '_sbmc_p' + ext))
         llpm0 = up(self._load(llpm_fn))
         self.gt = up(self._load(self.gt_fn))
-        h, w = self.kpcn.shape[:2]
+        h, w = self.gt.shape[:2]
         self.h, self.w = h, w
         # datasets.py:1407-1414: the first llpm file, all its samples: bounce type of the first bounce (descriptor 24)
         hit = (llpm0[..., 1:].mean(2)[..., 24:25] != 0.0).float()
         self.has_hit = torch.cat((hit,) * 3, dim=2)
-        self.llpm = None
-        if use_llpm_buf:
-            parts, s, i = [llpm0], llpm0.shape[2], 0
-            while s < spp:                                       # _load_all_spp_buffer
-                i += 1
-                parts.append(up(self._load(llpm_fn[:-4] + '_' + str(i) + '.npy')))
-                s += parts[-1].shape[2]
-            self.llpm = (torch.cat(parts, dim=2) if len(parts) > 1 else llpm0)[:, :, :spp].contiguous()
+        self.llpm = all_spp(llpm_fn, llpm0) if use_llpm_buf else None
         del llpm0
-        albedo = self.kpcn[..., 34:37] + 0.00316
-        self.full_ipt = self.kpcn[..., :3] * albedo + torch.exp(self.kpcn[..., 10:13]) - 1      # datasets.py:1234
+        if base_model == self.KPCN:
+            albedo = self.kpcn[..., 34:37] + 0.00316
+            self.full_ipt = self.kpcn[..., :3] * albedo + torch.exp(self.kpcn[..., 10:13]) - 1      # datasets.py:1234
+        else:
+            self.full_ipt = self.sbmc_s[..., :3].mean(2)                                             # datasets.py:1248
         self.full_tgt = self.gt[..., 0:3]
         self.coords = tile_coords(h, w, self.PATCH_SIZE, self.PAD_SIZE)
         _ops.check_tile_coords(self.coords, h, w, self.PATCH_SIZE)
@@ -169,7 +232,11 @@ class FullImageDataset:
         """Tiles [k * batch_size, (k + 1) * batch_size): the patch dictionary (datasets.py:1296-1297 on the device) and the
         device tile table."""
         sl = slice(k * self.batch_size, (k + 1) * self.batch_size)
-        batch = _ops.assemble_kpcn_patches(self.kpcn, self.llpm, self.gt, self.origins_dev[sl], self.PATCH_SIZE)
+        if self.base_model == self.KPCN:
+            batch = _ops.assemble_kpcn_patches(self.kpcn, self.llpm, self.gt, self.origins_dev[sl], self.PATCH_SIZE)
+        else:                        # (the tile table passed ``check_tile_coords``: every tile lies inside the frame)
+            batch = _ops.assemble_sample_patches(self.sbmc_s, self.sbmc_p, self.llpm, self.gt, self.origins_dev[sl], self.PATCH_SIZE,
+                                                 self.use_g_buf, self.use_sbmc_buf, check_origins=False)
         return batch, self.coords_dev[sl]
 
     def tile_batches(self):
@@ -181,6 +248,13 @@ class FullImageDataset:
             batch, _ = self.batch(k)
             cs = list(zip(*self.coords[k * self.batch_size:(k + 1) * self.batch_size]))
             yield (batch,) + tuple(list(c) for c in cs)
+
+
+class SampleFullImageDataset(FullImageDataset):
+    """``FullImageDataset`` for ``base_model`` 'sbmc' / 'lbmc' (``datasets.py:1193-1196, 1323-1351, 1364-1416``): the files of
+    ``_load_full_buffer`` with ``has_hit``, tiles of the sample-based dictionary.  A class of its own because ``FullImageDataset``
+    keeps refusing these models, as ``evaluate.py`` does: nothing in this package can denoise their tiles."""
+    SAMPLE_BASED = True
 
 
 # ------------------------------------------------------------------------------------------------- dataset directories
@@ -220,14 +294,14 @@ class _PendingProb:
 
 
 class DenoiseDirectory:
-    """The directory and file layer of the reference's ``DenoiseDataset`` (``datasets.py:161-283, 584-715``) for the KPCN base
-    model: renderer output under ``<gt_base_dir>/<mode>/{gt,input}/<scene>.npy`` (gt (H, W, 9), input (H, W, S, 104)).
+    """The directory and file layer of the reference's ``DenoiseDataset`` (``datasets.py:161-283, 584-715``) for the base model
+    ``base_model`` ('kpcn', the default; 'sbmc'; 'lbmc' = 'sbmc' with the g-buffer and without the SBMC buffers): renderer output under ``<gt_base_dir>/<mode>/{gt,input}/<scene>.npy`` (gt (H, W, 9), input (H, W, S, 104)).
 
       * discovery: the ``.npy`` files of ``<mode>/gt`` in sorted order (``os.walk`` lists in the file system's order; sorting
         makes a run repeatable), then the reference's seeded shuffle (``shuffled_files``);
       * path rules, as ``FullImageDataset``: ``/gt/`` <-> ``/input/``, and ``/KPCN/`` -> ``/LLPM/`` for the ``_llpm`` files;
       * no ``get_valid_path`` fallback across mounts: a missing file is a ``FileNotFoundError``;
-      * ``offline_preprocess`` writes what ``_offline_preprocess`` writes, minus the SBMC buffers, computed on the device;
+      * ``offline_preprocess`` writes what ``_offline_preprocess`` writes (the SBMC buffers with ``sbmc=True``), computed on the device;
       * ``reader`` / ``staged_hook`` feed ``support.loader.PatchLoader``; ``origins`` are the grid windows of validation.
 
     Training runs at the one sample count ``spp``; the reference's ``MSDenoiseDataset`` concatenation over 2..spp is not built.
@@ -236,8 +310,10 @@ class DenoiseDirectory:
     PATCH_SIZE = PatchBatcher.PATCH_SIZE
 
     def __init__(self, gt_base_dir, spp, mode='train', batch_size=8, sampling='random', use_llpm_buf=False, device=None,
-                 pnet_out_size=3, patch_size=PATCH_SIZE):
+                 pnet_out_size=3, patch_size=PATCH_SIZE, base_model='kpcn', use_g_buf=True, use_sbmc_buf=True):
         import os
+        # 'lbmc' is 'sbmc' with use_sbmc_buf=False, use_g_buf=True (datasets.py:171-174)
+        self.base_model, self.use_g_buf, self.use_sbmc_buf = sample_flags(base_model, use_g_buf, use_sbmc_buf)
         if mode not in ('train', 'val', 'test'):
             raise RuntimeError("Unknown training mode %s" % mode)
         if sampling not in ('random', 'grid'):
@@ -251,7 +327,7 @@ class DenoiseDirectory:
         self.use_llpm_buf, self.device, self.patch_size = use_llpm_buf, device, patch_size
         self.pnet_in_size = 36 if use_llpm_buf else 0                    # datasets.py:201-219
         self.pnet_out_size = pnet_out_size
-        self.dncnn_in_size = 34 + (pnet_out_size + 2 if use_llpm_buf else 0)
+        self.dncnn_in_size = dncnn_in_size(self.base_model, self.use_g_buf, self.use_sbmc_buf, use_llpm_buf, pnet_out_size)
         self.patches_per_image = (256 // batch_size) * batch_size if sampling == 'random' else 100      # datasets.py:273-279
         self.pre = DenoisePreprocessor(self.MAX_DEPTH)
 
@@ -261,13 +337,18 @@ class DenoiseDirectory:
     # ---- names
     def paths(self, i):
         """The file names that belong to image ``i`` (datasets.py:602-607, :633-634): 'gt', 'in', 'llpm', 'prob', and the
-        functions 'kpcn'(spp), 'in_k'(k), 'llpm_k'(k) of the per-spp and continuation files."""
+        functions 'kpcn'(spp), 'in_k'(k), 'llpm_k'(k) of the per-spp and continuation files; 'sbmc_s' / 'sbmc_p' with ``/KPCN/`` ->
+        ``/SBMC/`` (:1046-1049) and their continuation names 'sbmc_s_k'(k) / 'sbmc_p_k'(k)."""
         import os
         gt_fn = self.gt_files[i]
         in_fn = gt_fn.replace(os.sep + 'gt' + os.sep, os.sep + 'input' + os.sep)
         stem, ext = in_fn[:in_fn.rfind('.')], in_fn[in_fn.rfind('.'):]
         to_llpm = lambda fn: fn.replace(os.sep + 'KPCN' + os.sep, os.sep + 'LLPM' + os.sep)      # noqa: E731
+        to_sbmc = lambda fn: fn.replace(os.sep + 'KPCN' + os.sep, os.sep + 'SBMC' + os.sep)      # noqa: E731
         return {'gt': gt_fn, 'in': in_fn, 'llpm': to_llpm(stem + '_llpm' + ext), 'prob': stem + '_prob_imp' + ext,
+                'sbmc_s': to_sbmc(stem + '_sbmc_s' + ext), 'sbmc_p': to_sbmc(stem + '_sbmc_p' + ext),
+                'sbmc_s_k': lambda k: to_sbmc(stem + '_sbmc_s_' + str(k) + ext),
+                'sbmc_p_k': lambda k: to_sbmc(stem + '_sbmc_p_' + str(k) + ext),
                 'kpcn': lambda s: stem + '_kpcn_' + str(s) + ext, 'in_k': lambda k: stem + '_' + str(k) + ext,
                 'llpm_k': lambda k: to_llpm(stem + '_llpm_' + str(k) + ext)}
 
@@ -307,8 +388,11 @@ class DenoiseDirectory:
         return _ops.sanitize_(torch.from_numpy(a).to(self._device()))
 
     # ---- offline writer
-    def offline_preprocess(self, llpm=True, kpcn=True, overwrite=False, report=None):
-        """``_offline_preprocess`` (datasets.py:584-715) without the SBMC buffers.  Per scene: ``_llpm.npy`` (and ``_llpm_<k>.npy``
+    def offline_preprocess(self, llpm=True, kpcn=True, overwrite=False, report=None, sbmc=False):
+        """``_offline_preprocess`` (datasets.py:584-715).  ``sbmc=True`` writes ``_sbmc_s.npy`` / ``_sbmc_p.npy`` (:643-651) from the
+        main file cut to ``spp`` -- in the test mode too, where the reference raises ``NameError`` (it computes the buffers outside
+        the test mode only) -- and, an addition, ``_sbmc_s_<k>.npy`` / ``_sbmc_p_<k>.npy`` for the continuation files that exist:
+        ``_load_all_spp_buffer`` (:1302-1317) expects them beside ``_llpm_<k>.npy``.  Per scene: ``_llpm.npy`` (and ``_llpm_<k>.npy``
         for the continuation files ``<scene>_<k>.npy`` that exist, k = 1..7), ``_kpcn_<s>.npy`` for s in 2..spp (train / val) or the
         s of 2, 4, 8, 16, 32, 64 that the samples on disk reach (test), the gt file sanitised, and ``_prob_imp.npy`` outside the
         test mode.  A file that exists is kept unless ``overwrite``; a scene whose files all exist is not read at all.  Each raw
@@ -346,6 +430,15 @@ class DenoiseDirectory:
                     if want(p['llpm_k'](k)):
                         self._save(p['llpm_k'](k), self.pre._preprocess_llpm(raw(k)).cpu().numpy())
                         written.append(p['llpm_k'](k))
+            if sbmc:
+                for k in [0] + conts:
+                    fs, fp = (p['sbmc_s'], p['sbmc_p']) if k == 0 else (p['sbmc_s_k'](k), p['sbmc_p_k'](k))
+                    if want(fs) or want(fp):
+                        bs, bp = self.pre._preprocess_sbmc(raw(k))
+                        for fn, buf in ((fs, bs), (fp, bp)):
+                            if want(fn):
+                                self._save(fn, buf.cpu().numpy())
+                                written.append(fn)
             if kpcn:
                 # samples on disk, read once per scene: the main file's first spp (it holds at least spp), then the
                 # continuation files in order
@@ -424,7 +517,9 @@ class DenoiseDirectory:
         """Validation batches: every WHOLE window of the grid (the reference's ragged edge windows cannot be batched), image by
         image, ``batch_size`` at a time."""
         bs = self.batch_size if batch_size is None else batch_size
-        batcher = PatchBatcher(self.patch_size, bs)
+        sample_based = self.base_model == 'sbmc'
+        batcher = SamplePatchBatcher(self.patch_size, bs, self.use_g_buf, self.use_sbmc_buf) if sample_based \
+            else PatchBatcher(self.patch_size, bs)
         for i in (range(len(self)) if indices is None else indices):
             item = self.reader(i)
             d_raw, d_gt = self._upload(item['raw']), self._upload(item['gt'])
@@ -434,8 +529,13 @@ class DenoiseDirectory:
             if len(o) == 0:
                 raise ValueError("DenoiseDirectory: the %d x %d image %s holds no whole %d-pixel window"
                                  % (h, w, self.gt_files[i], self.patch_size))
-            kp = self.pre._preprocess_kpcn(d_raw)
             ll = self.pre._preprocess_llpm(d_raw) if self.use_llpm_buf else None
+            if sample_based:
+                ss, sp = self.pre._preprocess_sbmc(d_raw)
+                for k in range(0, len(o), bs):
+                    yield batcher.batch(ss, sp, ll, d_gt, o[k:k + bs])
+                continue
+            kp = self.pre._preprocess_kpcn(d_raw)
             for k in range(0, len(o), bs):
                 yield batcher.batch(kp, ll, d_gt, o[k:k + bs])
 

@@ -28,7 +28,7 @@ import threading
 import numpy as np
 import torch
 
-from .datasets import DenoisePreprocessor, PatchBatcher
+from .datasets import DenoisePreprocessor, PatchBatcher, SamplePatchBatcher, sample_flags
 
 
 class HostReaderPool:
@@ -111,13 +111,15 @@ class ImageStager:
     arrays (any object with the buffer protocol that ``torch.from_numpy`` / ``np.asarray`` accepts, e.g. a memmap)."""
 
     def __init__(self, reader, indices, device, depth=2, use_llpm=True, max_depth=DenoisePreprocessor.MAX_DEPTH, workers=2,
-                 staged_hook=None):
+                 staged_hook=None, base_model='kpcn'):
         """workers: reader / staging threads (``HostReaderPool``): images i + 1 .. i + workers are read from disk and copied
         into pinned memory concurrently while image i crosses PCIe.
         staged_hook: optional ``hook(d_raw, d_gt, prob) -> prob``, called on the copy stream once the frame is on the device and
         before the preprocessing kernels (``DenoiseDirectory.staged_hook``: sanitise the frame in place, compute and write a
-        missing probability map).  Without one the staged frame is preprocessed as it is."""
+        missing probability map).  Without one the staged frame is preprocessed as it is.
+        base_model: 'sbmc' / 'lbmc' iterate ``(sbmc_s (H,W,S,27), sbmc_p (H,W,S,66), llpm | None, gt, prob)`` instead."""
         assert depth >= 2, "double buffering needs two staging slots"
+        self.base_model = sample_flags(base_model)[0]
         self.workers = max(1, int(workers))
         self.reader, self.indices, self.device = reader, list(indices), torch.device(device)
         if self.device.index is None:                                 # 'cuda' -> the current device, by index (threads need it)
@@ -159,13 +161,16 @@ class ImageStager:
                     d_gt = p_gt.to(self.device, non_blocking=True)
                     if self.staged_hook is not None:
                         prob = self.staged_hook(d_raw, d_gt, prob)
-                    kpcn = self.pre._preprocess_kpcn(d_raw)
+                    if self.base_model == 'sbmc':
+                        bufs = self.pre._preprocess_sbmc(d_raw)
+                    else:
+                        bufs = (self.pre._preprocess_kpcn(d_raw),)
                     llpm = self.pre._preprocess_llpm(d_raw) if self.use_llpm else None
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 slot['event'] = ev
                 self.bytes_moved += nbytes
-                if not self._put(out_q, (kpcn, llpm, d_gt, prob, ev, slot), stop):
+                if not self._put(out_q, bufs + (llpm, d_gt, prob, ev, slot), stop):
                     return
             self._put(out_q, None, stop)
         except BaseException as exc:                                  # surface reader / CUDA errors in the consumer
@@ -183,14 +188,14 @@ class ImageStager:
                     return
                 if isinstance(got, BaseException):
                     raise got
-                kpcn, llpm, gt, prob, ev, slot = got
+                *bufs, prob, ev, slot = got                           # (kpcn | sbmc_s, sbmc_p), llpm, gt
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)                                    # the consumer's stream, not the host, waits
-                for t in (kpcn, llpm, gt):
+                for t in bufs:
                     if t is not None:
                         t.record_stream(cur)
                 hostpool.release(slot)                                # (its event guards the pinned buffers' reuse)
-                yield kpcn, llpm, gt, prob
+                yield tuple(bufs) + (prob,)
         finally:
             stop.set()                                                # the producer's queue waits poll this flag ...
             hostpool.stop.set()
@@ -199,13 +204,17 @@ class ImageStager:
 
 
 class PatchLoader:
-    """Batches of the KPCN base model over the staged images; ``len()`` = batches per epoch."""
+    """Batches of the KPCN base model -- or, with ``base_model`` 'sbmc' / 'lbmc', of the sample-based models (``use_g_buf`` /
+    ``use_sbmc_buf`` as ``DenoiseDataset`` resolves them) -- over the staged images; ``len()`` = batches per epoch."""
 
     def __init__(self, reader, indices, device, batch_size=8, patch_size=PatchBatcher.PATCH_SIZE, use_llpm=True, depth=2,
-                 patches_per_image=None, prefetch=2, workers=2, staged_hook=None):
+                 patches_per_image=None, prefetch=2, workers=2, staged_hook=None, base_model='kpcn', use_g_buf=True,
+                 use_sbmc_buf=True):
+        base_model, use_g_buf, use_sbmc_buf = sample_flags(base_model, use_g_buf, use_sbmc_buf)
         self.stager = ImageStager(reader, indices, device, depth=depth, use_llpm=use_llpm, workers=workers,
-                                  staged_hook=staged_hook)
-        self.batcher = PatchBatcher(patch_size, batch_size)
+                                  staged_hook=staged_hook, base_model=base_model)
+        self.batcher = SamplePatchBatcher(patch_size, batch_size, use_g_buf, use_sbmc_buf) if base_model == 'sbmc' \
+            else PatchBatcher(patch_size, batch_size)
         if patches_per_image is not None:
             self.batcher.patches_per_image = (patches_per_image // batch_size) * batch_size
         self.batch_size = batch_size
@@ -243,8 +252,8 @@ class PatchLoader:
                     got = next(images, None)
                 if got is None:
                     break
-                kpcn, llpm, gt, prob = got
-                h, w = kpcn.shape[:2]
+                *bufs, prob = got                                 # (kpcn | sbmc_s, sbmc_p), llpm, gt
+                h, w = bufs[0].shape[:2]
                 if prob is not None and np.shape(prob) == (h - p, w - p):
                     # a map over patch ORIGINS, cropped as `_prob_imp.npy` is (datasets.py:713): the reference's own draw
                     origins = self.batcher.sample_origins(np.asarray(prob))
@@ -269,7 +278,7 @@ class PatchLoader:
                             self._paced = False           # no kick within the timeout: this consumer does not pace -- stop waiting for it
                         if stop.is_set():
                             return
-                        batch = self.batcher.batch(kpcn, llpm, gt, origins_dev[k:k + self.batch_size], check=False)
+                        batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False)
                         ev = torch.cuda.Event()
                         ev.record(side)
                         if not ImageStager._put(out_q, (batch, ev), stop):
