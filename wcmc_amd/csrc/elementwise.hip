@@ -97,25 +97,34 @@ __device__ __forceinline__ float4 f4_mask(float4 a, int c, int C) {
   const NhwvIndex ix_ = decode_nhwv(idx_, total_, (H), (W), (C4));              \
   const int c = ix_.v * 4, x = ix_.x, y = ix_.y, n = ix_.n;
 
+// max of a 2x2 window the way ATen's max_pool2d forms it: the running maximum is replaced by a LARGER value or by a NaN, so a NaN in
+// the window reaches the output (fmaxf would drop it and the non-finite check of the step would never see it)
+__device__ __forceinline__ float max4(float a, float b, float d, float e) {
+  float m = a;
+  if (b > m || b != b) m = b;
+  if (d > m || d != d) m = d;
+  if (e > m || e != e) m = e;
+  return m;
+}
 __global__ void maxpool2_fwd_kernel(View in, MView out, int N, int Ho, int Wo, int C4, int C) {
   WCMC_ITER_NHWC(N, Ho, Wo, C4) {
     WCMC_DECODE_NHWC(Ho, Wo, C4)
     const float4 a = ld4(in, n, 2 * y, 2 * x, c), b = ld4(in, n, 2 * y, 2 * x + 1, c);
     const float4 d = ld4(in, n, 2 * y + 1, 2 * x, c), e = ld4(in, n, 2 * y + 1, 2 * x + 1, c);
-    float4 m = make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(d.x, e.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(d.y, e.y)),
-                           fmaxf(fmaxf(a.z, b.z), fmaxf(d.z, e.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(d.w, e.w)));
+    float4 m = make_float4(max4(a.x, b.x, d.x, e.x), max4(a.y, b.y, d.y, e.y), max4(a.z, b.z, d.z, e.z), max4(a.w, b.w, d.w, e.w));
     st4(out, n, y, x, c, f4_mask(m, c, C));
   }
 }
 
-// first maximum in window order (0,0),(0,1),(1,0),(1,1) takes the gradient, as ATen's max_pool2d does
+// first maximum in window order (0,0),(0,1),(1,0),(1,1) takes the gradient, as ATen's max_pool2d does; a NaN replaces the running
+// maximum like a larger value does (max4 above), so with NaNs in the window the LAST of them takes the gradient
 __device__ __forceinline__ void route4(float a, float b, float d, float e, float g, float& ga, float& gb, float& gd,
                                        float& ge) {
   ga = gb = gd = ge = 0.f;
   float m = a; int k = 0;
-  if (b > m) { m = b; k = 1; }
-  if (d > m) { m = d; k = 2; }
-  if (e > m) { m = e; k = 3; }
+  if (b > m || b != b) { m = b; k = 1; }
+  if (d > m || d != d) { m = d; k = 2; }
+  if (e > m || e != e) { m = e; k = 3; }
   if (k == 0) ga = g; else if (k == 1) gb = g; else if (k == 2) gd = g; else ge = g;
 }
 // add.p != null: dx = route(dy) + add -- the pooled tensor's input also feeds a skip connection (sbmc Autoencoder), whose gradient
