@@ -594,6 +594,33 @@ int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sbmc_p, const
                                  const int* origins, int B, int H, int W, int S, int P, int use_g_buf, int use_sbmc_buf,
                                  float* radiance, float* features, float* paths, float* target_image, void* stream);
 
+/* ---------------------------------------------------------------- sample counts 2..spp from one staged frame (csrc/multi_spp.hip)
+ * The reference trains over MSDenoiseDataset (support/datasets.py:1149-1171): one DenoiseDataset per count s = 2..spp, each reading
+ * the first s samples of every frame (:618, :1053-1054, :1091).  These entry points get every count out of ONE staged frame.
+ * wcmc_preprocess_kpcn_prefix: replaces `_preprocess_kpcn(sample[:, :, :s])` (:487-582) for s = s_lo..s_hi, 1 <= s_lo <= s_hi <=
+ *   S <= 64.  raw (h, w, S, C) as for wcmc_preprocess_kpcn -> out (s_hi - s_lo + 1, h, w, 44): slab s - s_lo is what
+ *   wcmc_preprocess_kpcn returns for the contiguous first s samples -- mean and population variance over the prefix (:505-543), the
+ *   divisions by that s, the depth normalised by that prefix's own image maximum, the gradients of that slab.  Sums run in sample
+ *   order (numpy's; wcmc_preprocess_kpcn's for a count that is no power of two), so a power-of-two count may differ from
+ *   wcmc_preprocess_kpcn's shuffle tree in the last place.  raw is read from memory once.
+ * wcmc_assemble_kpcn_patches_prefix / wcmc_assemble_sample_patches_prefix: wcmc_assemble_kpcn_patches / wcmc_assemble_sample_patches
+ *   where llpm, sbmc_s and sbmc_p hold S_total samples per pixel and the batch takes the first s, 1 <= s <= S_total: what
+ *   `llpm[:, :, :s]`, `sbmc_s[:, :, :s]`, `sbmc_p[:, :, :s]` feed DenoiseDataset.__getitem__ (:1045-1118).  paths / radiance /
+ *   features have s samples; the path-weight channel of the KPCN inputs is the mean over the first s, summed in sample order
+ *   (:1099-1107).  s == S_total is the plain entry point bit for bit.  llpm given needs paths (S_total is not read without llpm in
+ *   the KPCN form, but must still hold s). */
+size_t wcmc_preprocess_kpcn_prefix_workspace_bytes(int h, int w, int n_counts);
+int wcmc_preprocess_kpcn_prefix(const float* raw, int h, int w, int S, int C, int max_depth, int s_lo, int s_hi, float* out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int wcmc_assemble_kpcn_patches_prefix(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H,
+                                      int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
+                                      float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
+                                      float* target_diffuse, float* target_specular, float* target_total, void* stream);
+int wcmc_assemble_sample_patches_prefix(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
+                                        const int* origins, int B, int H, int W, int S_total, int s, int P, int use_g_buf,
+                                        int use_sbmc_buf, float* radiance, float* features, float* paths, float* target_image,
+                                        void* stream);
+
 /* ---------------------------------------------------------------- full-frame evaluation
  * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
  * (scene, spp) cell.  out / ipt / tgt: fp32 (H, W, 3) images, element (y, x, c) at p[y*sh + x*sw + c*sc] (any int64

@@ -115,6 +115,10 @@ SIGNATURES = {
     "wcmc_sanitize": (I, [P, L, P]),
     "wcmc_preprocess_sbmc": (I, [P, L, I, I, P, P, I, P]),
     "wcmc_assemble_sample_patches": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "wcmc_preprocess_kpcn_prefix_workspace_bytes": (Z, [I, I, I]),
+    "wcmc_preprocess_kpcn_prefix": (I, [P, I, I, I, I, I, I, I, P, P, Z, P]),
+    "wcmc_assemble_kpcn_patches_prefix": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "wcmc_assemble_sample_patches_prefix": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
     "wcmc_image_eval_workspace_bytes": (Z, [I, I]),
     "wcmc_image_eval": (I, [P, L, L, L, P, L, L, L, P, L, L, L, P, L, L, L, I, I, D, P, P, Z, P]),
     "wcmc_stitch_tiles": (I, [P, L, L, L, L, I, I, P, P, I, I, I, P, I, I, I, P, P, P, P]),

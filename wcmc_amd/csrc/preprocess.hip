@@ -7,20 +7,9 @@
 //   DenoiseDataset._gradients       :286-300   backward differences with a zero first column / row
 // Raw channel map: datasets.py:223-267 (C = 38 + 11 * (MAX_DEPTH + 1) = 104 at MAX_DEPTH = 5).
 // All three are streaming, HBM-bound kernels: the raw buffer (416 B per sample) is read once per function.
-#include "common.h"
+#include "data_step.h"
 
 namespace wcmc {
-
-struct PPMap { int radiance, diffuse, bounce, albedo, normal, depth, pweight, rwow, light, thr, rough, d; };
-
-static PPMap pp_map(int max_depth) {
-  const int d = max_depth + 1;
-  PPMap m;
-  m.radiance = 2; m.diffuse = 5; m.bounce = 24 + d * 6; m.albedo = 24 + d * 7; m.normal = 27 + d * 7;
-  m.depth = 30 + d * 7; m.pweight = 31 + d * 7; m.rwow = 32 + d * 7; m.light = 35 + d * 7;
-  m.thr = 38 + d * 7; m.rough = 38 + d * 10; m.d = d;
-  return m;
-}
 
 // generic form: one thread per (sample, output channel)
 __device__ __forceinline__ float pp_llpm_value(const float* r, int c, const PPMap& m, int base) {
@@ -102,9 +91,6 @@ __device__ __forceinline__ void pp_mean_var(const float* __restrict__ px, int s,
   for (int c = 0; c < NC; ++c) var[c] = sum[c] / (float)s;
 }
 
-// output channel offsets of the 44-channel KPCN buffer
-constexpr int KP_DIFF = 0, KP_SPEC = 10, KP_NORM = 20, KP_DEPTH = 30, KP_ALB = 34, KP_C = 44;
-
 // pass 1: everything that needs only the pixel's own samples; depth stays raw in the workspace
 __global__ __launch_bounds__(256) void pp_kpcn_stats_kernel(const float* __restrict__ raw, float* __restrict__ out,
                                                             float* __restrict__ ws, int64_t npix, int s, int C, PPMap m) {
@@ -157,7 +143,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* __restrict__ raw, float* __restrict__ out,
                                                                   float* __restrict__ ws, int64_t npix, int s, int C,
                                                                   PPMap m) {
-  const float eps = 0.00316f, spp = (float)s;
+  const float spp = (float)s;
   const int ppw = 64 / s;                                       // pixels per wave
   const int lane = threadIdx.x & 63, k = lane & (s - 1), pl = lane / s;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -167,30 +153,8 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* _
     const int64_t p = p0 + pl;
     const bool ok = p < npix;
     const float* r = raw + ((ok ? p : npix - 1) * s + k) * C;
-    // v: normal(3) depth(1) albedo(3) diffuse+(3) specular+(3)
-    float v[13], in[13];       // in: radiance(3) diffuse(3) albedo(3) normal(3) depth(1)
-    if (VEC) {                 // 16-byte aligned records, albedo at an even channel with albedo+2 a multiple of 4
-      const float2 a = *reinterpret_cast<const float2*>(r + 2), b = *reinterpret_cast<const float2*>(r + 4),
-                   c2 = *reinterpret_cast<const float2*>(r + 6), d2 = *reinterpret_cast<const float2*>(r + m.albedo);
-      const float4 e = *reinterpret_cast<const float4*>(r + m.albedo + 2);
-      in[0] = a.x; in[1] = a.y; in[2] = b.x; in[3] = b.y; in[4] = c2.x; in[5] = c2.y;
-      in[6] = d2.x; in[7] = d2.y; in[8] = e.x; in[9] = e.y; in[10] = e.z; in[11] = e.w; in[12] = r[m.depth];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        in[c] = r[m.radiance + c]; in[3 + c] = r[m.diffuse + c]; in[6 + c] = r[m.albedo + c]; in[9 + c] = r[m.normal + c];
-      }
-      in[12] = r[m.depth];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      v[c] = in[9 + c];
-      v[4 + c] = in[6 + c];
-      const float df = fmaxf(in[3 + c], 0.f);
-      v[7 + c] = df;
-      v[10 + c] = fmaxf(fmaxf(in[c], 0.f) - df, 0.f);
-    }
-    v[3] = in[12];
+    float v[13];               // normal(3) depth(1) albedo(3) diffuse+(3) specular+(3)
+    pp_kpcn_values<VEC>(r, m, v);
     float mean[13], var[13];
 #pragma unroll
     for (int c = 0; c < 13; ++c) {
@@ -203,21 +167,8 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* _
       var[c] = q / spp;
     }
     if (ok && k == 0) {
-      float* o = out + p * KP_C;
-      o[KP_NORM + 0] = mean[0]; o[KP_NORM + 1] = mean[1]; o[KP_NORM + 2] = mean[2];
-      o[KP_NORM + 3] = ((var[0] + var[1] + var[2]) / 3.0f) / spp;
-      ws[2 * p] = mean[3]; ws[2 * p + 1] = var[3];
+      pp_kpcn_write_stats(out + p * KP_C, ws + 2 * p, mean, var, spp);
       bmax = fmaxf(bmax, mean[3]);
-      o[KP_ALB + 0] = mean[4]; o[KP_ALB + 1] = mean[5]; o[KP_ALB + 2] = mean[6];
-      o[KP_ALB + 3] = ((var[4] + var[5] + var[6]) / 3.0f) / spp;
-      const float a0 = mean[4] + eps, a1 = mean[5] + eps, a2 = mean[6] + eps;
-      const float albedo_sqr = (a0 * a0 + a1 * a1 + a2 * a2) / 3.0f;
-      o[KP_DIFF + 0] = mean[7] / a0; o[KP_DIFF + 1] = mean[8] / a1; o[KP_DIFF + 2] = mean[9] / a2;
-      o[KP_DIFF + 3] = (((var[7] + var[8] + var[9]) / 3.0f) / spp) / albedo_sqr;
-      const float s0 = 1.0f + mean[10], s1 = 1.0f + mean[11], s2 = 1.0f + mean[12];
-      const float specular_sqr = (s0 * s0 + s1 * s1 + s2 * s2) / 3.0f;
-      o[KP_SPEC + 0] = logf(s0); o[KP_SPEC + 1] = logf(s1); o[KP_SPEC + 2] = logf(s2);
-      o[KP_SPEC + 3] = (((var[10] + var[11] + var[12]) / 3.0f) / spp) / specular_sqr;
     }
   }
   bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
@@ -226,44 +177,10 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* _
   if (lane == 0) atomicMax(reinterpret_cast<int*>(ws + 2 * npix), __float_as_int(bmax));
 }
 
-// pass 2: depth normalisation + clip, and the backward differences of the five feature groups.  One thread per
-// (pixel, output channel): a wave touches consecutive floats of the 176-byte pixel records.
+// pass 2 (data_step.h: pp_kpcn_finish)
 __global__ __launch_bounds__(256) void pp_kpcn_finish_kernel(float* __restrict__ out, const float* __restrict__ ws, int h,
                                                              int w, int s) {
-  const int64_t npix = (int64_t)h * w;
-  const float maxd = ws[2 * npix];
-  auto depth_of = [&](int64_t p) {
-    float d = ws[2 * p];
-    if (maxd > 0.f) d = d / maxd;
-    return fminf(fmaxf(d, 0.f), 1.f);
-  };
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < npix * KP_C;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = idx / KP_C;
-    const int c = (int)(idx - p * KP_C);
-    const int x = (int)(p % w), y = (int)(p / w);
-    if (c >= KP_DEPTH && c < KP_ALB) {
-      float v;
-      if (c == KP_DEPTH) v = depth_of(p);
-      else if (c == KP_DEPTH + 1) { v = ws[2 * p + 1]; if (maxd > 0.f) v = v / (maxd * maxd * (float)s); }
-      else if (c == KP_DEPTH + 2) v = x > 0 ? depth_of(p) - depth_of(p - 1) : 0.f;
-      else v = y > 0 ? depth_of(p) - depth_of(p - w) : 0.f;
-      out[idx] = v;
-      continue;
-    }
-    const int g0 = c < KP_SPEC ? KP_DIFF : c < KP_NORM ? KP_SPEC : c < KP_DEPTH ? KP_NORM : KP_ALB;
-    const int j = c - g0;
-    if (j < 4) continue;                                  // values and variance: final since pass 1
-    const int src = g0 + (j < 7 ? j - 4 : j - 7);
-    const float v = out[p * KP_C + src];
-    if (j < 7) out[idx] = x > 0 ? v - out[(p - 1) * KP_C + src] : 0.f;
-    else out[idx] = y > 0 ? v - out[(p - w) * KP_C + src] : 0.f;
-  }
-}
-
-static unsigned pp_grid(int64_t work) {
-  const int64_t b = ceil_div64(work, 256);
-  return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+  pp_kpcn_finish(out, ws, h, w, s);
 }
 
 }  // namespace wcmc
@@ -312,8 +229,7 @@ extern "C" int wcmc_preprocess_kpcn(const float* raw, int h, int w, int s, int C
     set_error("preprocess_kpcn: memset failed");
     return WCMC_ERR_LAUNCH;
   }
-  const bool vec = C % 4 == 0 && aligned16(raw) && m.radiance == 2 && m.diffuse == 5 && m.albedo % 2 == 0 &&
-                   (m.albedo + 2) % 4 == 0 && m.normal == m.albedo + 3 && m.depth == m.albedo + 6;
+  const bool vec = pp_kpcn_vec_ok(raw, C, m);
   if (s <= 64 && (s & (s - 1)) == 0 && vec)
     hipLaunchKernelGGL(pp_kpcn_stats_lanes_kernel<true>, dim3(pp_grid(npix * s)), dim3(256), 0, st, raw, out, ws, npix, s, C, m);
   else if (s <= 64 && (s & (s - 1)) == 0)
@@ -342,7 +258,8 @@ struct PatchOut {
 };
 __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __restrict__ kpcn, const float* __restrict__ llpm,
                                                                const float* __restrict__ gt, const int* __restrict__ origins,
-                                                               PatchOut o, int B, int H, int W, int S, int P) {
+                                                               PatchOut o, int B, int H, int W, int S, int Sn, int P) {
+  // S: samples per pixel of llpm; Sn <= S: the first Sn of them go to the batch
   const int64_t total = (int64_t)B * P * P;
   const int cin = llpm ? 35 : 34;
   const int64_t plane = (int64_t)P * P;
@@ -365,12 +282,12 @@ __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __re
     if (llpm) {
       const float* l = llpm + pix * S * 37;
       float pw = 0.f;
-      for (int s = 0; s < S; ++s) {
+      for (int s = 0; s < Sn; ++s) {
         pw += l[s * 37];
-        float* pp = o.paths + (((int64_t)b * S + s) * 36) * plane + po;
+        float* pp = o.paths + (((int64_t)b * Sn + s) * 36) * plane + po;
         for (int ch = 0; ch < 36; ++ch) pp[ch * plane] = l[s * 37 + 1 + ch];
       }
-      pw /= (float)S;
+      pw /= (float)Sn;
       din[34 * plane] = pw;
       sin[34 * plane] = pw;
     }
@@ -383,6 +300,19 @@ __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __re
     }
   }
 }
+
+int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H, int W,
+                            int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+                            float* specular_buffer, float* albedo, float* paths, float* target_diffuse, float* target_specular,
+                            float* target_total, hipStream_t stream) {
+  PatchOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths, target_diffuse, target_specular,
+             target_total};
+  const int64_t total = (int64_t)B * P * P;
+  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  hipLaunchKernelGGL(pp_assemble_kpcn_kernel, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, o, B, H, W, S_total, s,
+                     P);
+  return check_launch("assemble_kpcn_patches");
+}
 }  // namespace wcmc
 
 extern "C" int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float* gt, const int* origins,
@@ -394,11 +324,7 @@ extern "C" int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, 
                    specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse && target_specular &&
                    target_total && (!llpm || (paths && S > 0)),
                WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: bad argument");
-  wcmc::PatchOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths, target_diffuse,
-                   target_specular, target_total};
-  const int64_t total = (int64_t)B * P * P;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-  hipLaunchKernelGGL(wcmc::pp_assemble_kpcn_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, gt, origins, o,
-                     B, H, W, S, P);
-  return wcmc::check_launch("assemble_kpcn_patches");
+  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, B, H, W, S, S, P, diffuse_in, specular_in, diffuse_buffer,
+                                       specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
+                                       (hipStream_t)stream);
 }

@@ -5,7 +5,7 @@
 //   DenoiseDataset.__getitem__      :1045-1073, 1086-1118 + _transpose :760-791
 //                                              crop, channel selection and the (y,x,s,c) -> (s,c,y,x) transpose of a patch
 // Raw channel map: datasets.py:223-267.  Both are streaming, HBM-bound kernels: nothing is read twice.
-#include "common.h"
+#include "data_step.h"
 
 namespace wcmc {
 
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void sb_preprocess_tiled_kernel(const float* _
 constexpr int SA_XT = 32, SA_SC = 4;
 constexpr int SA_CP = 66, SA_CL = 37, SA_CG = 9;
 
-struct SampleSrc { const float* p; int C, S, nout; int64_t first; };     // first: index of the source's first work unit
+struct SampleSrc { const float* p; int C, S, Sp, nout; int64_t first; };  // S: samples taken, of the Sp each pixel holds; first: index of the source's first work unit
 struct SampleBatch {
   SampleSrc src[4];                                                      // sbmc_s, sbmc_p, llpm, gt (nout = 0: not read)
   float *rad, *feat, *paths, *tgt;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const i
     // (the host checks the origins; the clamp keeps a bad one from reading outside the image)
     const int r = min(max(origins[2 * b], 0), H - P) + y, c = min(max(origins[2 * b + 1], 0), W - P) + x0;
     const int run = scnt * sr.C, LD = (SA_SC * sr.C) | 1;
-    const int64_t pitch = (int64_t)sr.S * sr.C;
+    const int64_t pitch = (int64_t)sr.Sp * sr.C;
     const float* base = sr.p + ((int64_t)r * W + c) * pitch + (int64_t)s0 * sr.C;
     for (int f = threadIdx.x; f < xcnt * run; f += 256) {
       const int px = f / run, e = f - px * run;
@@ -142,6 +142,29 @@ __global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const i
 static unsigned sb_grid(int64_t work) {
   const int64_t b = ceil_div64(work, 256);
   return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
+int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins, int B,
+                       int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
+                       float* paths, float* target_image, hipStream_t stream) {
+  SampleBatch a;
+  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = target_image;
+  a.ng = use_g_buf ? 24 : 3;
+  a.F = a.ng + (use_sbmc_buf ? SA_CP : 0) + (llpm ? 1 : 0);
+  a.src[0] = SampleSrc{sbmc_s, SB_S, s, S_total, 3 + a.ng, 0};
+  a.src[1] = SampleSrc{sbmc_p, SA_CP, s, S_total, use_sbmc_buf ? SA_CP : 0, 0};
+  a.src[2] = SampleSrc{llpm, SA_CL, s, S_total, llpm ? SA_CL : 0, 0};
+  a.src[3] = SampleSrc{gt, SA_CG, 1, 1, 3, 0};
+  const int64_t rows = (int64_t)B * P * ((P + SA_XT - 1) / SA_XT);
+  int64_t units = 0;
+  for (int k = 0; k < 4; ++k) {
+    a.src[k].first = units;
+    if (a.src[k].nout > 0) units += rows * ((a.src[k].S + SA_SC - 1) / SA_SC);
+  }
+  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
+  hipLaunchKernelGGL(sa_assemble_kernel, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins, units,
+                     B, H, W, s, P);
+  return check_launch("assemble_sample_patches");
 }
 
 }  // namespace wcmc
@@ -176,22 +199,6 @@ extern "C" int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sb
   WCMC_REQUIRE(sbmc_s && gt && origins && B > 0 && H > 0 && W > 0 && S > 0 && P > 0 && P <= H && P <= W && radiance &&
                    features && target_image && (!use_sbmc_buf || sbmc_p) && (!llpm || paths),
                WCMC_ERR_BAD_ARG, "assemble_sample_patches: bad argument");
-  SampleBatch a;
-  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = target_image;
-  a.ng = use_g_buf ? 24 : 3;
-  a.F = a.ng + (use_sbmc_buf ? SA_CP : 0) + (llpm ? 1 : 0);
-  a.src[0] = SampleSrc{sbmc_s, SB_S, S, 3 + a.ng, 0};
-  a.src[1] = SampleSrc{sbmc_p, SA_CP, S, use_sbmc_buf ? SA_CP : 0, 0};
-  a.src[2] = SampleSrc{llpm, SA_CL, S, llpm ? SA_CL : 0, 0};
-  a.src[3] = SampleSrc{gt, SA_CG, 1, 3, 0};
-  const int64_t rows = (int64_t)B * P * ((P + SA_XT - 1) / SA_XT);
-  int64_t units = 0;
-  for (int k = 0; k < 4; ++k) {
-    a.src[k].first = units;
-    if (a.src[k].nout > 0) units += rows * ((a.src[k].S + SA_SC - 1) / SA_SC);
-  }
-  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  hipLaunchKernelGGL(sa_assemble_kernel, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, (hipStream_t)stream, a,
-                     origins, units, B, H, W, S, P);
-  return check_launch("assemble_sample_patches");
+  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, B, H, W, S, S, P, use_g_buf, use_sbmc_buf, radiance, features, paths,
+                            target_image, (hipStream_t)stream);
 }

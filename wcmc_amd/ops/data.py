@@ -1,6 +1,6 @@
 """The data step on the device: preprocessing and patch assembly (csrc/preprocess.hip), the sampling maps (csrc/sampling_map.hip),
-the buffers and batches of the sample-based denoisers (csrc/sbmc_data.hip), permutations, and the tile stitching of full-frame
-inference."""
+the buffers and batches of the sample-based denoisers (csrc/sbmc_data.hip), every sample count of a frame from one pass
+(csrc/multi_spp.hip), permutations, and the tile stitching of full-frame inference."""
 import ctypes
 import math
 
@@ -38,9 +38,36 @@ def preprocess_kpcn(sample, max_depth=5):
     return out
 
 
-def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch):
+def preprocess_kpcn_prefix(raw, s_lo, s_hi, max_depth=5):
+    """``_preprocess_kpcn(raw[:, :, :s])`` for every s in s_lo..s_hi from one read of the frame (``wcmc_preprocess_kpcn_prefix``;
+    what ``MSDenoiseDataset``, datasets.py:1149-1171, computes once per count): raw (h,w,S,C), 1 <= s_lo <= s_hi <= S <= 64 ->
+    (s_hi - s_lo + 1, h, w, 44); slab ``s - s_lo`` is ``preprocess_kpcn(raw[:, :, :s].contiguous())`` up to the order of the sums.
+    A view with another storage offset is taken as it is (records that are not 16-byte aligned take the scalar loads)."""
+    _need_dense(raw, 4)
+    h, w, s, c = raw.shape
+    s_lo, s_hi = int(s_lo), int(s_hi)
+    if not 1 <= s_lo <= s_hi <= s or s > 64:
+        raise ValueError("preprocess_kpcn_prefix: the counts must satisfy 1 <= s_lo <= s_hi <= S <= 64, got %d, %d and S = %d"
+                         % (s_lo, s_hi, s))
+    n = s_hi - s_lo + 1
+    out = torch.empty((n, h, w, 44), device=raw.device, dtype=torch.float32)
+    nbytes = lib().wcmc_preprocess_kpcn_prefix_workspace_bytes(h, w, n)
+    ws = torch.empty((nbytes + 3) // 4, device=raw.device, dtype=torch.float32)
+    check(lib().wcmc_preprocess_kpcn_prefix(_ptr(raw), h, w, s, c, max_depth, s_lo, s_hi, _ptr(out), _ptr(ws), ws.numel() * 4,
+                                            _stream()), "preprocess_kpcn_prefix")
+    return out
+
+
+def _check_prefix(who, spp, s_total):
+    if not 1 <= int(spp) <= s_total:
+        raise ValueError("%s: spp = %d is not a prefix of the %d samples the buffers hold" % (who, spp, s_total))
+    return int(spp)
+
+
+def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
     """The batch dictionary of the KPCN base model for windows of `patch` pixels at `origins` ((B, 2) int32 device
-    tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device)."""
+    tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device).  ``spp``: the batch takes
+    the first ``spp`` of llpm's samples (``wcmc_assemble_kpcn_patches_prefix``; ``kpcn`` is then that count's buffer); None: all."""
     _need_cuda(kpcn, gt)
     if not origins.is_cuda:
         raise RuntimeError("assemble_kpcn_patches: origins must be a device tensor")
@@ -51,6 +78,9 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch):
     if llpm is not None:
         assert llpm.shape[:2] == (h, w) and llpm.shape[3] == 37 and llpm.is_contiguous()
         s = llpm.shape[2]
+    s_total = s
+    if spp is not None and llpm is not None:
+        s = _check_prefix("assemble_kpcn_patches", spp, s_total)
     dev = kpcn.device
     cin = 35 if llpm is not None else 34
     shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
@@ -67,12 +97,14 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch):
     for k, shp in shapes.items():
         out[k] = flat[off:off + math.prod(shp)].view(shp)
         off += sizes[k]
-    check(lib().wcmc_assemble_kpcn_patches(_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w,
-                                           s, patch, _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
-                                           _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
-                                           _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
-                                           _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream()),
-          "assemble_kpcn_patches")
+    outs = (_ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]), _ptr(out["kpcn_diffuse_buffer"]),
+            _ptr(out["kpcn_specular_buffer"]), _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
+            _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream())
+    ins = (_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
+    if spp is not None and llpm is not None:
+        check(lib().wcmc_assemble_kpcn_patches_prefix(*ins, s_total, s, patch, *outs), "assemble_kpcn_patches_prefix")
+    else:                                             # (without llpm nothing in the batch depends on the sample count)
+        check(lib().wcmc_assemble_kpcn_patches(*ins, s, patch, *outs), "assemble_kpcn_patches")
     return out
 
 
@@ -102,12 +134,14 @@ def sample_feature_size(use_g_buf=True, use_sbmc_buf=True, use_llpm_buf=False):
     return (24 if use_g_buf else 3) + (66 if use_sbmc_buf else 0) + (1 if use_llpm_buf else 0)
 
 
-def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True):
+def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True,
+                            spp=None):
     """The batch dictionary of the SBMC / LBMC interfaces (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and
     ``target_image``) for windows of ``patch`` pixels at ``origins`` ((B, 2) int32 (row, column); numpy or tensor) of one image's
     buffers (datasets.py:1045-1073, 1086-1118 and ``_transpose`` on the device, one launch).  ``sbmc_p`` may be None without
     ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  ``check_origins=False``: the caller has checked them
-    on the host (checking a device tensor here synchronises)."""
+    on the host (checking a device tensor here synchronises).  ``spp``: the batch takes the first ``spp`` samples of the buffers
+    (``wcmc_assemble_sample_patches_prefix``: the buffers are per-sample, so the prefix is a slice); None: all of them."""
     _need_cuda(sbmc_s, gt)
     h, w, s = sbmc_s.shape[:3]
     if tuple(sbmc_s.shape) != (h, w, s, 27) or tuple(gt.shape) != (h, w, 9) or not (sbmc_s.is_contiguous() and gt.is_contiguous()):
@@ -129,6 +163,9 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
     origins = origins.to(sbmc_s.device, torch.int32).contiguous()
     assert origins.dim() == 2 and origins.shape[1] == 2
     b = origins.shape[0]
+    s_total = s
+    if spp is not None:
+        s = _check_prefix("assemble_sample_patches", spp, s_total)
     f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
     shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
     if llpm is not None:
@@ -141,11 +178,13 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
     for k, shp in shapes.items():
         out[k] = flat[off:off + math.prod(shp)].view(shp)
         off += sizes[k]
-    check(lib().wcmc_assemble_sample_patches(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt),
-                                             ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, int(bool(use_g_buf)),
-                                             int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
-                                             _ptr(out.get("paths")), _ptr(out["target_image"]), _stream()),
-          "assemble_sample_patches")
+    ins = (_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
+    outs = (patch, int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
+            _ptr(out.get("paths")), _ptr(out["target_image"]), _stream())
+    if spp is not None:
+        check(lib().wcmc_assemble_sample_patches_prefix(*ins, s_total, s, *outs), "assemble_sample_patches_prefix")
+    else:
+        check(lib().wcmc_assemble_sample_patches(*ins, s, *outs), "assemble_sample_patches")
     return out
 
 

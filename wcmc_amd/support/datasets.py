@@ -33,6 +33,11 @@ class DenoisePreprocessor:
         gradients (datasets.py:487-582)."""
         return _ops.preprocess_kpcn(sample, self.max_depth)
 
+    def _preprocess_kpcn_prefix(self, sample, s_lo, s_hi):
+        """raw (h, w, S, 104) -> (s_hi - s_lo + 1, h, w, 44): ``_preprocess_kpcn(sample[:, :, :s])`` for s = s_lo..s_hi from one read
+        of the frame -- what ``MSDenoiseDataset`` (datasets.py:1149-1171) computes once per count."""
+        return _ops.preprocess_kpcn_prefix(sample, s_lo, s_hi, self.max_depth)
+
     def _preprocess_sbmc(self, sample):
         """sanitised raw (h, w, s, 104) -> (sbmc_s (h, w, s, 27), sbmc_p (h, w, s, 66)): per-sample radiance, log radiance, log
         specular, subpixel and g-buffer; log sampling probabilities, clipped light directions and the five planes of
@@ -72,9 +77,10 @@ class SamplePatchBatcher:
     def check_origins(self, origins, h, w):
         _ops.check_patch_origins(origins, h, w, self.patch_size, who="SamplePatchBatcher")
 
-    def batch(self, sbmc_s, sbmc_p, llpm, gt, origins, check=True):
+    def batch(self, sbmc_s, sbmc_p, llpm, gt, origins, check=True, spp=None):
+        """``spp``: the first ``spp`` samples of the buffers (datasets.py:1053-1054, 1091); None: all of them."""
         return _ops.assemble_sample_patches(sbmc_s, sbmc_p if self.use_sbmc_buf else None, llpm, gt, origins, self.patch_size,
-                                            self.use_g_buf, self.use_sbmc_buf, check_origins=check)
+                                            self.use_g_buf, self.use_sbmc_buf, check_origins=check, spp=spp)
 
 
 class PatchBatcher:
@@ -107,14 +113,15 @@ class PatchBatcher:
         if o.size and (int(o[:, 0].max()) + self.patch_size > h or int(o[:, 1].max()) + self.patch_size > w or int(o.min()) < 0):
             raise ValueError("PatchBatcher: a %d-pixel patch origin lies outside the %dx%d image" % (self.patch_size, h, w))
 
-    def batch(self, kpcn, llpm, gt, origins, check=True):
+    def batch(self, kpcn, llpm, gt, origins, check=True, spp=None):
         """kpcn (H,W,44), llpm (H,W,S,37) or None, gt (H,W,9): device tensors; origins: (B,2) rows/columns (numpy or
         tensor).  ``check=False``: the caller has run ``check_origins`` on them (``PatchLoader`` does, once per image, on the
-        host copy -- checking a device tensor here would synchronise every batch)."""
+        host copy -- checking a device tensor here would synchronise every batch).  ``spp``: ``kpcn`` is the buffer of the first
+        ``spp`` samples and the batch takes that prefix of ``llpm`` (datasets.py:1091); None: all of its samples."""
         if check:
             self.check_origins(origins, *kpcn.shape[:2])
         o = torch.as_tensor(np.asarray(origins), dtype=torch.int32) if not isinstance(origins, torch.Tensor) else origins
-        return _ops.assemble_kpcn_patches(kpcn, llpm, gt, o.to(kpcn.device, torch.int32).contiguous(), self.patch_size)
+        return _ops.assemble_kpcn_patches(kpcn, llpm, gt, o.to(kpcn.device, torch.int32).contiguous(), self.patch_size, spp=spp)
 
 
 SamplePatchBatcher.sample_origins = PatchBatcher.sample_origins
@@ -285,6 +292,21 @@ def sanitized(a):
     return np.where(a < np.float32(1.0e+38), a, np.float32(1.0e+38)).astype(np.float32)
 
 
+def multi_counts(spp):
+    """The sample counts of ``MSDenoiseDataset(..., spp, ...)`` (datasets.py:1157-1171): 2..spp; below 2 its ``RuntimeError``."""
+    if spp < 2:
+        raise RuntimeError("spp too low to randomize sample count")
+    return tuple(range(2, int(spp) + 1))
+
+
+def check_counts(counts, s_total):
+    """``counts`` as an ascending tuple of distinct sample counts in 1..s_total."""
+    counts = tuple(int(s) for s in counts)
+    if not counts or list(counts) != sorted(set(counts)) or counts[0] < 1 or counts[-1] > s_total:
+        raise ValueError("counts must be ascending, distinct sample counts in 1..%d, got %s" % (s_total, counts))
+    return counts
+
+
 class _PendingProb:
     """What ``DenoiseDirectory.reader`` returns for 'prob' while ``_prob_imp.npy`` does not exist: ``staged_hook`` computes the
     map from the staged frame and writes ``fn``."""
@@ -304,7 +326,9 @@ class DenoiseDirectory:
       * ``offline_preprocess`` writes what ``_offline_preprocess`` writes (the SBMC buffers with ``sbmc=True``), computed on the device;
       * ``reader`` / ``staged_hook`` feed ``support.loader.PatchLoader``; ``origins`` are the grid windows of validation.
 
-    Training runs at the one sample count ``spp``; the reference's ``MSDenoiseDataset`` concatenation over 2..spp is not built.
+    A directory is read at ``spp`` samples per pixel.  The reference's ``MSDenoiseDataset`` (datasets.py:1149-1171) -- every count
+    2..spp -- is ``counts=`` of ``support.loader.PatchLoader`` and of ``grid_batches``: the frame is staged once at ``spp`` samples
+    and every count comes out of it (``multi_counts``).
     """
     MAX_DEPTH = DenoisePreprocessor.MAX_DEPTH
     PATCH_SIZE = PatchBatcher.PATCH_SIZE
@@ -513,9 +537,12 @@ class DenoiseDirectory:
         h, w = self._load(self.gt_files[i], mmap=True).shape[:2]
         return grid_origins(h, w, self.patch_size)
 
-    def grid_batches(self, indices=None, batch_size=None):
+    def grid_batches(self, indices=None, batch_size=None, counts=None):
         """Validation batches: every WHOLE window of the grid (the reference's ragged edge windows cannot be batched), image by
-        image, ``batch_size`` at a time."""
+        image, ``batch_size`` at a time.  ``counts``: per image, the grid at every one of these sample counts (ascending) from one
+        upload and one prefix pass -- image-major, where ``MSDenoiseDataset`` walks all images per count: validation sums its
+        batches, so the order does not matter."""
+        counts = None if counts is None else check_counts(counts, self.spp)
         bs = self.batch_size if batch_size is None else batch_size
         sample_based = self.base_model == 'sbmc'
         batcher = SamplePatchBatcher(self.patch_size, bs, self.use_g_buf, self.use_sbmc_buf) if sample_based \
@@ -532,15 +559,25 @@ class DenoiseDirectory:
             ll = self.pre._preprocess_llpm(d_raw) if self.use_llpm_buf else None
             if sample_based:
                 ss, sp = self.pre._preprocess_sbmc(d_raw)
-                for k in range(0, len(o), bs):
-                    yield batcher.batch(ss, sp, ll, d_gt, o[k:k + bs])
+                for s in ([None] if counts is None else counts):
+                    for k in range(0, len(o), bs):
+                        yield batcher.batch(ss, sp, ll, d_gt, o[k:k + bs], spp=s)
                 continue
-            kp = self.pre._preprocess_kpcn(d_raw)
-            for k in range(0, len(o), bs):
-                yield batcher.batch(kp, ll, d_gt, o[k:k + bs])
+            if counts is None:
+                kp = self.pre._preprocess_kpcn(d_raw)
+                for k in range(0, len(o), bs):
+                    yield batcher.batch(kp, ll, d_gt, o[k:k + bs])
+                continue
+            slabs = self.pre._preprocess_kpcn_prefix(d_raw, counts[0], counts[-1])
+            for s in counts:
+                for k in range(0, len(o), bs):
+                    yield batcher.batch(slabs[s - counts[0]], ll, d_gt, o[k:k + bs], spp=s)
 
-    def num_grid_batches(self, indices=None, batch_size=None):
+    def num_grid_batches(self, indices=None, batch_size=None, counts=None):
         bs = self.batch_size if batch_size is None else batch_size
+        return self._num_grid_batches(indices, bs) * (1 if counts is None else len(check_counts(counts, self.spp)))
+
+    def _num_grid_batches(self, indices, bs):
         n = 0
         for i in (range(len(self)) if indices is None else indices):
             h, w = self._load(self.gt_files[i], mmap=True).shape[:2]

@@ -19,6 +19,9 @@ PCIe without stalling the training stream:
     side stream by a producer thread ``prefetch`` batches ahead of the consumer, which only makes its stream wait for the
     batch's event.
 
+With ``counts`` (the reference's ``MSDenoiseDataset`` over 2..spp, ``datasets.py:1149-1171``) an image is staged ONCE at the largest
+count and every count is drawn from it: ``multi_count_schedule`` is the order, DESIGN.md section 14 the reasoning.
+
 ``scripts/time_loader.py`` measures it (patches/s and PCIe GB/s) next to the train step's consumption rate.
 """
 import ctypes
@@ -28,7 +31,20 @@ import threading
 import numpy as np
 import torch
 
-from .datasets import DenoisePreprocessor, PatchBatcher, SamplePatchBatcher, sample_flags
+from .datasets import DenoisePreprocessor, PatchBatcher, SamplePatchBatcher, check_counts, sample_flags
+
+
+def multi_count_schedule(n_images, counts, window):
+    """The order in which a multi-count epoch visits ``(image, sample count)``: for each window of ``window`` consecutive images,
+    for each count ascending, for each image of the window.  ``window >= n_images`` is the reference's enumeration -- index ``i`` of
+    ``MSDenoiseDataset`` is image ``(i % (N * ppi)) // ppi`` at count ``2 + i // (N * ppi)`` (``datasets.py:1157-1171`` concatenates one
+    ``DenoiseDataset`` of ``N * ppi`` items per count, the loader does not shuffle) -- and needs every image's buffers resident at once;
+    ``window = 1`` is image-major and holds one."""
+    n_images, window = int(n_images), int(window)
+    if window < 1:
+        raise ValueError("multi_count_schedule: window must be at least 1, got %d" % window)
+    counts = sorted(int(s) for s in counts)
+    return [(i, s) for w0 in range(0, n_images, window) for s in counts for i in range(w0, min(w0 + window, n_images))]
 
 
 class HostReaderPool:
@@ -111,13 +127,17 @@ class ImageStager:
     arrays (any object with the buffer protocol that ``torch.from_numpy`` / ``np.asarray`` accepts, e.g. a memmap)."""
 
     def __init__(self, reader, indices, device, depth=2, use_llpm=True, max_depth=DenoisePreprocessor.MAX_DEPTH, workers=2,
-                 staged_hook=None, base_model='kpcn'):
+                 staged_hook=None, base_model='kpcn', counts=None):
         """workers: reader / staging threads (``HostReaderPool``): images i + 1 .. i + workers are read from disk and copied
         into pinned memory concurrently while image i crosses PCIe.
         staged_hook: optional ``hook(d_raw, d_gt, prob) -> prob``, called on the copy stream once the frame is on the device and
         before the preprocessing kernels (``DenoiseDirectory.staged_hook``: sanitise the frame in place, compute and write a
         missing probability map).  Without one the staged frame is preprocessed as it is.
-        base_model: 'sbmc' / 'lbmc' iterate ``(sbmc_s (H,W,S,27), sbmc_p (H,W,S,66), llpm | None, gt, prob)`` instead."""
+        base_model: 'sbmc' / 'lbmc' iterate ``(sbmc_s (H,W,S,27), sbmc_p (H,W,S,66), llpm | None, gt, prob)`` instead.
+        counts: ascending sample counts; the frame is kept at all its S >= max(counts) samples and, for 'kpcn', the stack
+        ``(max(counts) - min(counts) + 1, H, W, 44)`` of the buffers of EVERY count min..max (``_preprocess_kpcn_prefix``: one read of
+        the frame) stands in place of the single buffer -- slab ``s - min(counts)`` belongs to count ``s``.  llpm and the SBMC
+        buffers are per-sample and stay whole: a count is a prefix of them."""
         assert depth >= 2, "double buffering needs two staging slots"
         self.base_model = sample_flags(base_model)[0]
         self.workers = max(1, int(workers))
@@ -127,6 +147,7 @@ class ImageStager:
         self.depth, self.use_llpm = depth, use_llpm
         self.pre = DenoisePreprocessor(max_depth)
         self.staged_hook = staged_hook
+        self.counts = None if counts is None else check_counts(counts, 64)
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.bytes_moved = 0
 
@@ -163,6 +184,11 @@ class ImageStager:
                         prob = self.staged_hook(d_raw, d_gt, prob)
                     if self.base_model == 'sbmc':
                         bufs = self.pre._preprocess_sbmc(d_raw)
+                    elif self.counts is not None:
+                        if d_raw.shape[2] < self.counts[-1]:
+                            raise ValueError("ImageStager: the frame holds %d samples per pixel, fewer than the largest count %d"
+                                             % (d_raw.shape[2], self.counts[-1]))
+                        bufs = (self.pre._preprocess_kpcn_prefix(d_raw, self.counts[0], self.counts[-1]),)
                     else:
                         bufs = (self.pre._preprocess_kpcn(d_raw),)
                     llpm = self.pre._preprocess_llpm(d_raw) if self.use_llpm else None
@@ -205,14 +231,22 @@ class ImageStager:
 
 class PatchLoader:
     """Batches of the KPCN base model -- or, with ``base_model`` 'sbmc' / 'lbmc', of the sample-based models (``use_g_buf`` /
-    ``use_sbmc_buf`` as ``DenoiseDataset`` resolves them) -- over the staged images; ``len()`` = batches per epoch."""
+    ``use_sbmc_buf`` as ``DenoiseDataset`` resolves them) -- over the staged images; ``len()`` = batches per epoch.
+
+    ``counts`` (ascending sample counts, e.g. ``datasets.multi_counts(spp)``) and ``window``: the epoch walks
+    ``multi_count_schedule(len(indices), counts, window)``; every ``(image, count)`` gets ``patches_per_image`` patches at fresh
+    origins (the reference draws them per dataset, i.e. per count: ``datasets.py:795-810``) assembled from the first ``count``
+    samples of the image's buffers, so every batch has one sample count.  Up to ``window`` staged images stay resident;
+    ``report`` (e.g. ``print``) is told their footprint once."""
 
     def __init__(self, reader, indices, device, batch_size=8, patch_size=PatchBatcher.PATCH_SIZE, use_llpm=True, depth=2,
                  patches_per_image=None, prefetch=2, workers=2, staged_hook=None, base_model='kpcn', use_g_buf=True,
-                 use_sbmc_buf=True):
+                 use_sbmc_buf=True, counts=None, window=1, report=None):
         base_model, use_g_buf, use_sbmc_buf = sample_flags(base_model, use_g_buf, use_sbmc_buf)
         self.stager = ImageStager(reader, indices, device, depth=depth, use_llpm=use_llpm, workers=workers,
-                                  staged_hook=staged_hook, base_model=base_model)
+                                  staged_hook=staged_hook, base_model=base_model, counts=counts)
+        self.counts, self.window, self.report = self.stager.counts, max(1, int(window)), report
+        self.kpcn_slabs = base_model != 'sbmc'                        # the stager's first buffer is the stack of per-count buffers
         self.batcher = SamplePatchBatcher(patch_size, batch_size, use_g_buf, use_sbmc_buf) if base_model == 'sbmc' \
             else PatchBatcher(patch_size, batch_size)
         if patches_per_image is not None:
@@ -235,54 +269,104 @@ class PatchLoader:
         self._tick.release()
 
     def __len__(self):
-        return len(self.stager.indices) * (self.batcher.patches_per_image // self.batch_size)
+        return len(self.stager.indices) * (self.batcher.patches_per_image // self.batch_size) * (len(self.counts) if self.counts else 1)
+
+    def _origins(self, prob, h, w):
+        """One image's ``patches_per_image`` window origins, drawn from its probability map and checked."""
+        p = self.batcher.patch_size
+        if prob is not None and np.shape(prob) == (h - p, w - p):
+            # a map over patch ORIGINS, cropped as `_prob_imp.npy` is (datasets.py:713): the reference's own draw
+            origins = self.batcher.sample_origins(np.asarray(prob))
+        else:
+            if prob is None:
+                prob = np.zeros((h, w), dtype=np.float64)     # (not a distribution: uniform, as the reference falls back)
+            # origins must keep the window inside the image: the reference crops what it gets, which silently shrinks
+            # a patch at the border; its probability maps are zero there (datasets.py:795-810)
+            valid = np.zeros((h, w), dtype=np.float64)
+            valid[:h - p + 1, :w - p + 1] = np.asarray(prob, dtype=np.float64)[:h - p + 1, :w - p + 1]
+            s = valid.sum()
+            if s > 0:
+                valid /= s
+            else:
+                valid[:h - p + 1, :w - p + 1] = 1.0 / ((h - p + 1) * (w - p + 1))
+            origins = self.batcher.sample_origins(valid)
+        self.batcher.check_origins(origins, h, w)
+        return origins
+
+    def _assemble(self, bufs, origins, out_q, stop, spp=None):
+        """Enqueue the assembly of one image's batches on the side stream and hand them over; False: the consumer has gone."""
+        side = self.assemble_stream
+        with torch.cuda.stream(side):
+            origins_dev = torch.as_tensor(origins, dtype=torch.int32).to(self.stager.device)      # one copy per image
+            for k in range(0, len(origins), self.batch_size):
+                if self._paced and not self._tick.acquire(timeout=self.pace_timeout):
+                    self._paced = False           # no kick within the timeout: this consumer does not pace -- stop waiting for it
+                if stop.is_set():
+                    return False
+                if spp is None:
+                    batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False)
+                else:
+                    batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False, spp=spp)
+                ev = torch.cuda.Event()
+                ev.record(side)
+                if not ImageStager._put(out_q, (batch, ev), stop):
+                    return False
+        return True
+
+    @staticmethod
+    def footprint_bytes(bufs):
+        """Device bytes of one staged image's buffers."""
+        return sum(t.numel() * t.element_size() for t in bufs if isinstance(t, torch.Tensor))
+
+    def _produce_counts(self, images, out_q, stop):
+        """The multi-count epoch: walk ``multi_count_schedule``; an image is taken from the stager when the schedule first names it
+        and dropped when its window is over."""
+        side, held = self.assemble_stream, {}
+        for i, s in multi_count_schedule(len(self.stager.indices), self.counts, self.window):
+            if stop.is_set():
+                return False
+            if i not in held:
+                if i % self.window == 0:
+                    held.clear()                              # a new window: the last one's buffers go back to the allocator
+                with torch.cuda.stream(side):                 # (the stager hands its buffers to the CURRENT stream)
+                    got = next(images, None)
+                if got is None:
+                    raise RuntimeError("PatchLoader: the stager ran out of images before the schedule did")
+                held[i] = got
+                if self.report is not None:
+                    one = self.footprint_bytes(got)
+                    self.report("[] multi-count loader: %.1f MB of device buffers per staged image, a window of %d holds up to %.1f MB"
+                                % (one / 1e6, self.window, one * min(self.window, len(self.stager.indices)) / 1e6))
+                    self.report = None
+            *bufs, prob = held[i]
+            h, w = bufs[-1].shape[:2]                         # gt
+            origins = self._origins(prob, h, w)
+            if self.kpcn_slabs:
+                bufs[0] = bufs[0][s - self.counts[0]]
+            if not self._assemble(bufs, origins, out_q, stop, spp=s):
+                return False
+        return True
 
     def _produce(self, out_q, stop):
         """Producer thread: walks the staged images, draws an image's origins and enqueues the assembly of its batches on
         the side stream; hands ``(batch, event)`` to the consumer through a bounded queue."""
-        p = self.batcher.patch_size
         dev = self.stager.device
         side = self.assemble_stream
         images = None
         try:
             torch.cuda.set_device(dev)
             images = iter(self.stager)
-            while not stop.is_set():
+            if self.counts is not None and not self._produce_counts(images, out_q, stop):
+                return
+            while self.counts is None and not stop.is_set():
                 with torch.cuda.stream(side):                     # (the stager hands its buffers to the CURRENT stream)
                     got = next(images, None)
                 if got is None:
                     break
                 *bufs, prob = got                                 # (kpcn | sbmc_s, sbmc_p), llpm, gt
                 h, w = bufs[0].shape[:2]
-                if prob is not None and np.shape(prob) == (h - p, w - p):
-                    # a map over patch ORIGINS, cropped as `_prob_imp.npy` is (datasets.py:713): the reference's own draw
-                    origins = self.batcher.sample_origins(np.asarray(prob))
-                else:
-                    if prob is None:
-                        prob = np.zeros((h, w), dtype=np.float64)     # (not a distribution: uniform, as the reference falls back)
-                    # origins must keep the window inside the image: the reference crops what it gets, which silently shrinks
-                    # a patch at the border; its probability maps are zero there (datasets.py:795-810)
-                    valid = np.zeros((h, w), dtype=np.float64)
-                    valid[:h - p + 1, :w - p + 1] = np.asarray(prob, dtype=np.float64)[:h - p + 1, :w - p + 1]
-                    s = valid.sum()
-                    if s > 0:
-                        valid /= s
-                    else:
-                        valid[:h - p + 1, :w - p + 1] = 1.0 / ((h - p + 1) * (w - p + 1))
-                    origins = self.batcher.sample_origins(valid)
-                self.batcher.check_origins(origins, h, w)
-                with torch.cuda.stream(side):
-                    origins_dev = torch.as_tensor(origins, dtype=torch.int32).to(dev)      # one copy per image
-                    for k in range(0, len(origins), self.batch_size):
-                        if self._paced and not self._tick.acquire(timeout=self.pace_timeout):
-                            self._paced = False           # no kick within the timeout: this consumer does not pace -- stop waiting for it
-                        if stop.is_set():
-                            return
-                        batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False)
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        if not ImageStager._put(out_q, (batch, ev), stop):
-                            return
+                if not self._assemble(bufs, self._origins(prob, h, w), out_q, stop):
+                    return
             ImageStager._put(out_q, None, stop)
         except BaseException as exc:                              # surface reader / CUDA errors in the consumer
             ImageStager._put(out_q, exc, stop)

@@ -19,8 +19,10 @@ What differs, on purpose:
   * ``--graph`` replays one hipGraph per step (``wcmc_amd.graph.GraphedTrainStep``) when the loader keeps its shapes;
   * ``init_data`` feeds ``--synthetic N`` batches per epoch with the dataset's schema (``wcmc_amd.synthetic``) -- the default --
     or, with ``--from_data_dir``, the renderer output under ``--data_dir`` (``support/datasets.py:DenoiseDirectory`` through
-    ``support/loader.py:PatchLoader``) at the one sample count ``--num_samples``; the reference's ``MSDenoiseDataset``
-    concatenation over 2..spp is not built (INTEGRATION.md section 4).  ``train`` takes any iterable of batch dictionaries;
+    ``support/loader.py:PatchLoader``) at the one sample count ``--num_samples`` -- or, with ``--multi_spp``, at every count
+    2..``--num_samples`` as the reference's ``MSDenoiseDataset`` does (``train_kpcn.py:170-173``), each frame staged once and walked in
+    windows of ``--ms_window`` images.  ``train`` takes any iterable of batch
+    dictionaries;
   * no visdom (``--visual`` is accepted and ignored), no tqdm.
 """
 import argparse
@@ -52,6 +54,10 @@ def _to_device(batch, device):
     return batch
 
 
+def _batch_signature(batch):
+    return tuple(sorted((k, tuple(v.shape)) for k, v in batch.items() if isinstance(v, torch.Tensor)))
+
+
 def train_epoch_kpcn(epoch, interfaces, dataloaders, params, args):
     assert 'train' in dataloaders, "argument `dataloaders` dictionary should contain `'train'` key."
     assert 'data_device' in params, "argument `params` dictionary should contain `'data_device'` key."
@@ -59,12 +65,19 @@ def train_epoch_kpcn(epoch, interfaces, dataloaders, params, args):
     for itf in interfaces:
         itf.to_train_mode()
     steps = params.setdefault('graphed_steps', {})
+    shapes = params.setdefault('graphed_shapes', {})
     n = 0
     for batch in dataloaders['train']:
         batch = _to_device(batch, params['data_device'])
         for i, itf in enumerate(interfaces):
             if getattr(args, 'graph', False):
+                if i in steps and shapes.get(i) != _batch_signature(batch):
+                    # another sample count (--multi_spp): a captured step is its shapes.  The live step goes BEFORE the next one
+                    # is captured -- two live steps segfault
+                    steps[i].flush()
+                    steps.pop(i).close()
                 if i not in steps:
+                    shapes[i] = _batch_signature(batch)
                     from .graph import capture_validated
                     overlap = getattr(args, 'overlap_allreduce', False)
                     two = bool(getattr(itf, 'halves_supported', lambda: False)()) and not overlap and not getattr(args, 'one_graph', False)
@@ -135,7 +148,7 @@ def train(interfaces, dataloaders, params, args):
 
 
 def _picklable(params):
-    return {k: v for k, v in params.items() if k not in ('graphed_steps', 'group')}
+    return {k: v for k, v in params.items() if k not in ('graphed_steps', 'graphed_shapes', 'group')}
 
 
 # ------------------------------------------------------------------------------------------------- data
@@ -159,14 +172,23 @@ class SyntheticLoader:
 class GridValLoader:
     """``len``-able iterable over the whole grid windows of a ``DenoiseDirectory`` (``sampling='grid'``), ``BS_VAL`` at a time."""
 
-    def __init__(self, directory, indices, batch_size):
-        self.directory, self.indices, self.batch_size = directory, list(indices), batch_size
+    def __init__(self, directory, indices, batch_size, counts=None):
+        self.directory, self.indices, self.batch_size, self.counts = directory, list(indices), batch_size, counts
 
     def __len__(self):
-        return self.directory.num_grid_batches(self.indices, self.batch_size)
+        return self.directory.num_grid_batches(self.indices, self.batch_size, counts=self.counts)
 
     def __iter__(self):
-        return self.directory.grid_batches(self.indices, self.batch_size)
+        return self.directory.grid_batches(self.indices, self.batch_size, counts=self.counts)
+
+
+def multi_spp_loader_args(args, rank=0):
+    """``counts`` / ``window`` / ``report`` of ``PatchLoader`` and ``counts`` of ``GridValLoader`` under ``--multi_spp`` (else empty)."""
+    if not getattr(args, 'multi_spp', False):
+        return {}, None
+    from .support.datasets import multi_counts
+    counts = multi_counts(args.num_samples)                # RuntimeError below 2 spp, as datasets.py:1158-1160
+    return dict(counts=counts, window=args.ms_window, report=print if rank == 0 else None), counts
 
 
 def init_data_dir(args, device, rank=0, world=1):
@@ -182,10 +204,11 @@ def init_data_dir(args, device, rank=0, world=1):
         raise RuntimeError('%s holds %d training and %d validation images: fewer than the %d ranks'
                            % (args.data_dir, len(tr), len(va), world))
     shard = lambda d: range(rank, len(d) // world * world, world)                     # noqa: E731
+    ms, counts = multi_spp_loader_args(args, rank)
     train = PatchLoader(tr.reader, shard(tr), device, batch_size=args.batch_size, patch_size=args.patch_size,
                         use_llpm=args.use_llpm_buf, patches_per_image=getattr(args, 'patches_per_image', None),
-                        staged_hook=tr.staged_hook)
-    val = GridValLoader(va, shard(va), BS_VAL)
+                        staged_hook=tr.staged_hook, **ms)
+    val = GridValLoader(va, shard(va), BS_VAL, counts=counts)
     sizes = {'dncnn_in_size': tr.dncnn_in_size, 'pnet_in_size': PNET_IN, 'pnet_out_size': tr.pnet_out_size}
     return sizes, {'train': train, 'val': val}
 
@@ -288,7 +311,7 @@ def init_model(sizes, args, device, group=None):
 
 # ------------------------------------------------------------------------------------------------- command line
 def build_parser():
-    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0], epilog=MULTI_SPP_EPILOG)
     # support/utils.py:69-100 (BasicArgumentParser)
     p.add_argument('--sbmc', action='store_true')
     p.add_argument('--p_buf', action='store_true')
@@ -358,8 +381,52 @@ def build_parser():
     return p
 
 
+MS_WINDOW = 8       # default of --ms_window (0.5 s per capture against 4 GB per resident 1280 x 1280 image)
+
+
+MULTI_SPP_EPILOG = ('additions of this build, on train_kpcn, train_sbmc and train_lbmc alike: --multi_spp (with --from_data_dir: train '
+                    'and validate at every sample count 2..--num_samples) and --ms_window K (images kept on the device while the '
+                    'counts are walked over them; default %d)' % MS_WINDOW)
+
+
+def multi_spp_parser():
+    """``--multi_spp`` / ``--ms_window``: additions of this build (the reference always trains over 2..spp, ``train_kpcn.py:170-173``).
+    A parser of their own, read before the launcher's: ``build_parser()`` of each launcher stays the reference's flag surface plus
+    what earlier rounds added, which tests pin flag by flag."""
+    p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    p.add_argument('--multi_spp', action='store_true',
+                   help='an addition of this build; with --from_data_dir: train and validate at every sample count 2..--num_samples '
+                        "(the reference's MSDenoiseDataset) instead of the one count --num_samples; every frame is staged once")
+    p.add_argument('--ms_window', type=int, default=MS_WINDOW, metavar='K',
+                   help='an addition of this build; with --multi_spp: images whose buffers stay on the device while the counts are '
+                        'walked over them -- all counts of K images, then the next K.  K >= the number of training images is the '
+                        "reference's order; with --graph there is one capture per (window, count)")
+    return p
+
+
+def parse_args(argv=None, parser=None):
+    """The launcher's arguments: the two multi-count flags first, everything else by ``parser`` (default: ``build_parser()``)."""
+    ms, rest = multi_spp_parser().parse_known_args(argv)
+    args = (build_parser() if parser is None else parser).parse_args(rest)
+    for k, v in vars(ms).items():
+        setattr(args, k, v)
+    return args
+
+
+def check_multi_spp_args(args):
+    if getattr(args, 'multi_spp', False):
+        if not getattr(args, 'from_data_dir', False):
+            raise RuntimeError('`--multi_spp` draws its sample counts from the frames of a dataset directory: it needs '
+                               '`--from_data_dir`')
+        if args.ms_window < 1:
+            raise RuntimeError('`--ms_window` should be at least 1')
+        if args.num_samples < 2:
+            raise RuntimeError('spp too low to randomize sample count')                  # datasets.py:1158-1160
+
+
 def check_args(args):
     """The argument errors of ``train_kpcn.py:427-441``."""
+    check_multi_spp_args(args)
     if args.manif_learn and not args.use_llpm_buf:
         raise RuntimeError('The manifold learning module requires a llpm-specific buffer.')
     if args.manif_learn and not args.manif_loss:
@@ -379,7 +446,7 @@ def check_args(args):
 
 
 def main(argv=None):
-    args = check_args(build_parser().parse_args(argv))
+    args = check_args(parse_args(argv))
     rank, world, local = wd.init('nccl')
     device = torch.device('cuda', local if world > 1 else args.device_id)
     torch.cuda.set_device(device)

@@ -61,11 +61,11 @@ def init_model(sizes, args, device):
 
 
 def build_parser():
-    return ts.add_common_arguments(argparse.ArgumentParser(description=__doc__.split('\n')[0]), use_sbmc_buf=False)
+    return ts.add_common_arguments(argparse.ArgumentParser(description=__doc__.split('\n')[0], epilog=ts.tk.MULTI_SPP_EPILOG), use_sbmc_buf=False)
 
 
 def main(argv=None):
-    args = ts.check_args(build_parser().parse_args(argv))
+    args = ts.check_args(ts.tk.parse_args(argv, build_parser()))
     return ts.run(args, init_data, init_model)
 
 

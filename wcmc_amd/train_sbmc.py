@@ -12,7 +12,8 @@ What differs, on purpose:
     (B, S, n_in, h, w)) to a (B, 3, h', w') image.  No stand-in ships in the package (INTEGRATION.md);
   * data comes from ``--from_data_dir`` only (``support.datasets.DenoiseDirectory(base_model='sbmc')`` through
     ``support.loader.PatchLoader``: the SBMC buffers are computed on the device from the staged raw frame), at the one sample
-    count ``--num_samples``; the reference's ``MSDenoiseDataset`` concatenation over 2..8 spp is not built;
+    count ``--num_samples`` or, with ``--multi_spp``, at every count 2..``--num_samples`` as the reference's ``MSDenoiseDataset``
+    does (``train_sbmc.py:41-44``; the flags and the order: ``wcmc_amd.train_kpcn``, DESIGN.md section 14);
   * one process, one GPU; no visdom.
 
     python -m wcmc_amd.train_sbmc --from_data_dir --data_dir D --denoiser my_pkg.models:make_multisteps --desc ... --use_sbmc_buf
@@ -74,10 +75,11 @@ def init_data(args, device, base_model='sbmc', use_sbmc_buf=None):
               use_g_buf=True, use_sbmc_buf=use_sbmc_buf)
     tr = DenoiseDirectory(args.data_dir, args.num_samples, 'train', args.batch_size, 'random', **kw)
     va = DenoiseDirectory(args.data_dir, args.num_samples, 'val', BS_VAL, 'grid', **kw)
+    ms, counts = tk.multi_spp_loader_args(args)
     train = PatchLoader(tr.reader, range(len(tr)), device, batch_size=args.batch_size, patch_size=args.patch_size,
                         use_llpm=args.use_llpm_buf, patches_per_image=args.patches_per_image, staged_hook=tr.staged_hook,
-                        base_model=tr.base_model, use_g_buf=tr.use_g_buf, use_sbmc_buf=tr.use_sbmc_buf)
-    val = tk.GridValLoader(va, range(len(va)), BS_VAL)
+                        base_model=tr.base_model, use_g_buf=tr.use_g_buf, use_sbmc_buf=tr.use_sbmc_buf, **ms)
+    val = tk.GridValLoader(va, range(len(va)), BS_VAL, counts=counts)
     sizes = {'dncnn_in_size': tr.dncnn_in_size, 'pnet_in_size': tr.pnet_in_size, 'pnet_out_size': tr.pnet_out_size}
     return sizes, {'train': train, 'val': val}
 
@@ -211,7 +213,7 @@ def add_common_arguments(p, use_sbmc_buf):
 
 
 def build_parser():
-    return add_common_arguments(argparse.ArgumentParser(description=__doc__.split('\n')[0]), use_sbmc_buf=True)
+    return add_common_arguments(argparse.ArgumentParser(description=__doc__.split('\n')[0], epilog=tk.MULTI_SPP_EPILOG), use_sbmc_buf=True)
 
 
 def check_args(args):
@@ -236,7 +238,7 @@ def run(args, init_data_fn, init_model_fn):
 
 
 def main(argv=None):
-    args = check_args(build_parser().parse_args(argv))
+    args = check_args(tk.parse_args(argv, build_parser()))
     return run(args, init_data, init_model)
 
 
