@@ -86,7 +86,8 @@ __device__ __forceinline__ void pp_kpcn_finish(float* __restrict__ out, const fl
   auto depth_of = [&](int64_t p) {
     float d = ws[2 * p];
     if (maxd > 0.f) d = d / maxd;
-    return fminf(fmaxf(d, 0.f), 1.f);
+    // np.clip keeps a NaN (an overflowed mean over an overflowed maximum is Inf / Inf); fminf(fmaxf()) would turn it into 0
+    return d < 0.f ? 0.f : (d > 1.f ? 1.f : d);
   };
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < npix * KP_C;
        idx += (int64_t)gridDim.x * blockDim.x) {
