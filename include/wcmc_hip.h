@@ -650,6 +650,31 @@ int wcmc_stitch_tiles(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, i
                       const float* pbuf_a, const float* pbuf_b, int S, int C, int P, const int* coords, int B, int H, int W,
                       float* out_rad, float* out_pbuf_a, float* out_pbuf_b, void* stream);
 
+/* ---------------------------------------------------------------- denoising a render of any size (csrc/frame_tiles.hip)
+ * Inference on a frame with no ground truth and no divisibility condition (wcmc_amd.denoise, DESIGN.md "Denoising a render").
+ * The frame is taken as extended by `pad` pixels on every side by mirror reflection with the edge repeated -- numpy.pad's
+ * 'symmetric', the map of the reflect-index entry point above -- and tiled at stride P - 2*pad; every tile owns pixels of its
+ * [pad, P - pad) interior only, so nothing but what the network computed from real or mirrored data reaches the image.
+ * assemble_kpcn_tiles: the batch of the KPCN base model without targets, for B tiles of P x P pixels at origins[b] = (row, column)
+ *   in FRAME coordinates, -pad <= origin <= dim + pad - P (device int32 [B][2]; the caller checks them on the host), out of
+ *   kpcn (H, W, 44) and llpm (H, W, S, 37; null without --use_llpm_buf): diffuse_in / specular_in (B, 34 [+1], P, P), the two
+ *   3-channel radiance buffers, albedo + 0.00316 and paths (B, S, 36, P, P), laid out as the patch-assembly entry point lays them
+ *   out.  The extended frame is never stored: a position outside reads its mirror image's record, and each of the 26 backward
+ *   differences is taken again as value[m(r), m(c)] - value[m(r), m(c - 1)] (rows likewise; 0 at frame position -pad) wherever its two
+ *   operands are not in-frame neighbours.  Bit for bit what preprocessing numpy.pad(raw, pad, 'symmetric') and assembling patches at
+ *   origins + pad give.  0 <= pad < min(H, W), P > 2*pad, P <= min(H, W) + 2*pad.
+ * finish_frame: one pass over the frame after stitching.  out_rad (3, H, W), kpcn (H, W, 44), llpm (H, W, S, 37) ->
+ *   ipt (H, W, 3) = kpcn[0:3] * (kpcn[34:37] + 0.00316) + exp(kpcn[10:13]) - 1   (datasets.py:1234)
+ *   has_hit (H, W) = 1.0 where (sum over the S samples, in sample order, of llpm[..., 25]) / S != 0, else 0.0   (:1407-1414)
+ *   out (H, W, 3) = has_hit ? out_rad : ipt   (test_models.py:231-232)
+ *   preview_out / preview_ipt (H, W, 3) uint8, each optional (null: not written): round(255 * clip(tonemap(.), 0, 1)) of out / ipt
+ *   with tonemap of test_models.py:24-34 at gamma 1/2.2 on the image's own luminance, rounding half to even; NaN gives 0. */
+int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P, int pad,
+                             float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer, float* albedo,
+                             float* paths, void* stream);
+int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm, int H, int W, int S, float* out, float* ipt,
+                      float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

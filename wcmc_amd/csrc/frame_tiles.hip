@@ -1,0 +1,179 @@
+// Denoising a render of any size (wcmc_amd.denoise; DESIGN.md "Denoising a render"): the two kernels around the network.
+//
+//   wcmc_assemble_kpcn_tiles  the inference batch for tiles whose origins may lie up to `pad` pixels outside the frame.  The frame is
+//                             taken as extended by `pad` pixels on every side by mirror reflection with the edge repeated (numpy
+//                             'symmetric', scipy 'reflect': wcmc_reflect_index), but the extension is never stored: a position
+//                             outside reads the record of its mirror image, and the backward differences of the 44-channel buffer
+//                             (data_step.h: pp_kpcn_finish) are taken again from the stored values wherever a neighbour lies across
+//                             the edge.  Bit for bit what preprocessing the padded raw frame and wcmc_assemble_kpcn_patches give.
+//   wcmc_finish_frame         one pass over the stitched frame: the noisy input, the has-hit mask, the composite and 8-bit previews.
+#include "data_step.h"
+
+namespace wcmc {
+
+// source index of position i in [-n, 2n) of a line of n entries: d c b a | a b c d | d c b a (one reflection; pad < n).  The clamp
+// costs two instructions and keeps a table the host check let through from reading outside the buffers.
+__device__ __forceinline__ int ft_mirror(int i, int n) {
+  const int m = i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
+  return min(max(m, 0), n - 1);
+}
+
+struct TileOut {
+  float *din, *sin, *dbuf, *sbuf, *alb, *paths;
+};
+
+// value channel behind the g-th backward difference of a direction: diffuse, specular, normal (3 each), depth (1), albedo (3)
+__device__ __forceinline__ int ft_grad_src(int g) { return g < 3 ? KP_DIFF + g : g < 6 ? KP_SPEC + g - 3 : g < 9 ? KP_NORM + g - 6 :
+                                                           g < 10 ? KP_DEPTH : KP_ALB + g - 10; }
+// where that difference is stored: dx at value + 4 (depth: + 2), dy at value + 7 (depth: + 3)
+__device__ __forceinline__ int ft_grad_dst(int g, bool dy) {
+  const int src = ft_grad_src(g);
+  return src == KP_DEPTH ? src + (dy ? 3 : 2) : src + (dy ? 7 : 4);
+}
+
+// One thread per (tile, y, x), as pp_assemble_kpcn_kernel: every output plane is written as coalesced rows, each record is read once
+// (a second record's thirteen values only where a difference crosses the frame's edge: the outer `pad` ring of border tiles).
+template <bool VEC>
+__global__ __launch_bounds__(256) void ft_assemble_tiles_kernel(const float* __restrict__ kpcn, const float* __restrict__ llpm,
+                                                                const int* __restrict__ origins, TileOut o, int B, int H, int W,
+                                                                int S, int P, int pad) {
+  const int64_t total = (int64_t)B * P * P;
+  const int cin = llpm ? 35 : 34;
+  const int64_t plane = (int64_t)P * P;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % P), y = (int)((i / P) % P), b = (int)(i / plane);
+    const int r = origins[2 * b] + y, c = origins[2 * b + 1] + x;             // (row, column) of the frame; may lie outside
+    const int mr = ft_mirror(r, H), mc = ft_mirror(c, W);
+    const int64_t pix = (int64_t)mr * W + mc;
+    const float* k = kpcn + pix * KP_C;
+    float v[KP_C];
+    if (VEC) {
+#pragma unroll
+      for (int q = 0; q < KP_C / 4; ++q) {
+        const float4 t = *reinterpret_cast<const float4*>(k + 4 * q);
+        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+      }
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < KP_C; ++ch) v[ch] = k[ch];
+    }
+    // The stored difference is that of the extended frame only where both operands are in-frame neighbours (1 <= c < W); elsewhere
+    // it is value[m(r), m(c)] - value[m(r), m(c - 1)], and 0 in the extended frame's first column / row (frame position -pad).
+    if (c < 1 || c >= W) {
+      const bool first = c + pad <= 0;
+      const float* kl = kpcn + ((int64_t)mr * W + ft_mirror(c - 1, W)) * KP_C;
+#pragma unroll
+      for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, false)] = first ? 0.f : v[ft_grad_src(g)] - kl[ft_grad_src(g)];
+    }
+    if (r < 1 || r >= H) {
+      const bool first = r + pad <= 0;
+      const float* ku = kpcn + ((int64_t)ft_mirror(r - 1, H) * W + mc) * KP_C;
+#pragma unroll
+      for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, true)] = first ? 0.f : v[ft_grad_src(g)] - ku[ft_grad_src(g)];
+    }
+    const int64_t po = (int64_t)y * P + x;
+    float* din = o.din + (int64_t)b * cin * plane + po;
+    float* sin = o.sin + (int64_t)b * cin * plane + po;
+#pragma unroll
+    for (int ch = 0; ch < 10; ++ch) din[ch * plane] = v[ch];
+#pragma unroll
+    for (int ch = 20; ch < 44; ++ch) din[(ch - 10) * plane] = v[ch];
+#pragma unroll
+    for (int ch = 10; ch < 44; ++ch) sin[(ch - 10) * plane] = v[ch];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      o.dbuf[((int64_t)b * 3 + ch) * plane + po] = v[ch];
+      o.sbuf[((int64_t)b * 3 + ch) * plane + po] = v[10 + ch];
+      o.alb[((int64_t)b * 3 + ch) * plane + po] = v[34 + ch] + 0.00316f;
+    }
+    if (llpm) {
+      const float* l = llpm + pix * S * 37;
+      float pw = 0.f;
+      for (int s = 0; s < S; ++s) {
+        pw += l[s * 37];
+        float* pp = o.paths + (((int64_t)b * S + s) * 36) * plane + po;
+        for (int ch = 0; ch < 36; ++ch) pp[ch * plane] = l[s * 37 + 1 + ch];
+      }
+      pw /= (float)S;
+      din[34 * plane] = pw;
+      sin[34 * plane] = pw;
+    }
+  }
+}
+
+// tonemap of test_models.py:24-34 at its default gamma on the image's own luminance, then round(255 * .) (half to even, as np.round)
+__device__ __forceinline__ void ft_preview(const float* rgb, uint8_t* dst) {
+  const float lum = 0.2126f * rgb[0] + 0.7152f * rgb[1] + 0.0722f * rgb[2];
+  const float den = 1.f + lum / 1.5f;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float t = fmaxf(rgb[ch] / den, 0.f);                  // (fmaxf / fminf: a NaN becomes 0, a defined 8-bit value)
+    t = fminf(fmaxf(powf(t, 1.0f / 2.2f), 0.f), 1.f);
+    dst[ch] = (uint8_t)rintf(255.f * t);
+  }
+}
+
+// One thread per pixel.  llpm: one float per sample (descriptor 24 of `paths`: the bounce type of the first bounce).
+__global__ __launch_bounds__(256) void ft_finish_frame_kernel(const float* __restrict__ out_rad, const float* __restrict__ kpcn,
+                                                              const float* __restrict__ llpm, int64_t npix, int S,
+                                                              float* __restrict__ out, float* __restrict__ ipt,
+                                                              float* __restrict__ has_hit, uint8_t* __restrict__ prev_out,
+                                                              uint8_t* __restrict__ prev_ipt) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const float* k = kpcn + p * KP_C;
+    const float* l = llpm + p * S * 37 + 25;
+    float sum = 0.f;
+    for (int s = 0; s < S; ++s) sum += l[s * 37];
+    const bool hit = sum / (float)S != 0.f;
+    float in[3], res[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      in[ch] = k[KP_DIFF + ch] * (k[KP_ALB + ch] + 0.00316f) + expf(k[KP_SPEC + ch]) - 1.f;
+      res[ch] = hit ? out_rad[ch * npix + p] : in[ch];
+      ipt[p * 3 + ch] = in[ch];
+      out[p * 3 + ch] = res[ch];
+    }
+    has_hit[p] = hit ? 1.f : 0.f;
+    if (prev_out) ft_preview(res, prev_out + p * 3);
+    if (prev_ipt) ft_preview(in, prev_ipt + p * 3);
+  }
+}
+
+}  // namespace wcmc
+
+using namespace wcmc;
+
+extern "C" int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P,
+                                        int pad, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+                                        float* specular_buffer, float* albedo, float* paths, void* stream) {
+  WCMC_REQUIRE(kpcn && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles: null pointer");
+  WCMC_REQUIRE(!llpm || (paths && S > 0), WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: llpm needs a paths output and S > 0");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles: B, H, W, P must be positive and pad non-negative");
+  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
+  TileOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths};
+  const int64_t total = (int64_t)B * P * P;
+  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  if (aligned16(kpcn))
+    hipLaunchKernelGGL(ft_assemble_tiles_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B, H,
+                       W, S, P, pad);
+  else
+    hipLaunchKernelGGL(ft_assemble_tiles_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B, H,
+                       W, S, P, pad);
+  return check_launch("assemble_kpcn_tiles");
+}
+
+extern "C" int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm, int H, int W, int S, float* out,
+                                 float* ipt, float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream) {
+  WCMC_REQUIRE(out_rad && kpcn && llpm && out && ipt && has_hit, WCMC_ERR_BAD_ARG, "finish_frame: null pointer");
+  WCMC_REQUIRE(H > 0 && W > 0 && S > 0, WCMC_ERR_BAD_ARG, "finish_frame: H, W and S must be positive (got %d, %d, %d)", H, W, S);
+  const int64_t npix = (int64_t)H * W;
+  hipLaunchKernelGGL(ft_finish_frame_kernel, dim3(pp_grid(npix)), dim3(256), 0, (hipStream_t)stream, out_rad, kpcn, llpm, npix, S, out,
+                     ipt, has_hit, preview_out, preview_ipt);
+  return check_launch("finish_frame");
+}

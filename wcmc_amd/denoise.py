@@ -1,0 +1,226 @@
+"""Denoise raw renders of any size with a trained KPCN model: no ground truth, no offline files, every pixel.
+
+    python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
+        [--spp N] [--tile_batch B] [--png] [--save_pbuffer] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
+
+Per input file (renderer output (H, W, S, 104), H and W at least 64): the first ``--spp`` samples (default: what the file holds; a
+file that holds fewer is continued by ``<stem>_1.npy``, ``<stem>_2.npy``, ... beside it) are uploaded once, sanitised and
+preprocessed on the device; ``support.inference.denoise_frame`` runs the network over mirror-extended tiles and composites the
+result; ``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the
+result and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  The model flags are those of
+``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  Only the KPCN models are run here (SBMC / LBMC need the
+caller's base denoiser, as in ``wcmc_amd.evaluate``).  One line per frame reports the seconds of each phase.
+"""
+import os
+import struct
+import time
+import zlib
+
+import numpy as np
+import torch
+
+from . import ops, train_kpcn
+from .support.datasets import MAX_CONTINUATIONS, DenoisePreprocessor, dncnn_in_size
+from .support.inference import denoise_frame
+
+PATCH_SIZE, PAD_SIZE = 128, 32
+
+
+# ------------------------------------------------------------------------------------------------- image writers
+def write_pfm(fn, img):
+    """(H, W, 3) or (H, W) float image -> little-endian PFM (rows bottom to top, scale -1.0)."""
+    img = np.asarray(img, dtype='<f4')
+    if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3):
+        raise ValueError("write_pfm: the image should be (H, W) or (H, W, 3), got %s" % (img.shape,))
+    with open(fn, 'wb') as f:
+        f.write(b'%s\n%d %d\n-1.0\n' % (b'PF' if img.ndim == 3 else b'Pf', img.shape[1], img.shape[0]))
+        f.write(np.ascontiguousarray(img[::-1]).tobytes())
+
+
+def write_png(fn, img):
+    """(H, W, 3) uint8 image -> 8-bit RGB PNG, with the standard library alone (filter 0 on every row)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("write_png: the image should be (H, W, 3) uint8, got %s %s" % (img.dtype, img.shape))
+    h, w = img.shape[:2]
+    rows = np.concatenate((np.zeros((h, 1), np.uint8), img.reshape(h, w * 3)), axis=1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+    with open(fn, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+                + chunk(b'IDAT', zlib.compress(rows, 6)) + chunk(b'IEND', b''))
+
+
+# ------------------------------------------------------------------------------------------------- input
+def tile_batch_size(spp, tile_batch=None):
+    """Tiles per network call: 8 up to 32 spp, 4 up to 64 (test_models.py:147-161); above that the caller decides."""
+    if tile_batch is not None:
+        if tile_batch < 1:
+            raise ValueError("--tile_batch should be at least 1, got %d" % tile_batch)
+        return tile_batch
+    if spp <= 32:
+        return 8
+    if spp <= 64:
+        return 4
+    raise ValueError("no default tile batch size above 64 samples per pixel (got %d): give --tile_batch after looking at the "
+                     "device's memory" % spp)
+
+
+def _open_raw(fn):
+    if not os.path.isfile(fn):
+        raise FileNotFoundError(fn)
+    a = np.load(fn, mmap_mode='r')
+    if a.ndim != 4 or a.shape[-1] != 104:
+        raise ValueError("%s: shape %s is not renderer output (H, W, S, 104)" % (fn, tuple(a.shape)))
+    return a
+
+
+def read_raw(fn, spp=None):
+    """The memory-mapped parts ``[(H, W, s_k, 104)]`` that hold the first ``spp`` samples of frame ``fn`` (default: the samples in
+    the file), and ``spp``.  A file with fewer samples is continued by ``<stem>_1.npy``, ``<stem>_2.npy``, ... (datasets.py:632-640);
+    a series that ends before ``spp`` samples are there is a ``ValueError``."""
+    a = _open_raw(fn)
+    if spp is None:
+        spp = a.shape[2]
+    if spp < 1:
+        raise ValueError("--spp should be at least 1, got %d" % spp)
+    parts, have = [a[:, :, :spp]], min(a.shape[2], spp)
+    stem, ext = os.path.splitext(fn)
+    for k in range(1, MAX_CONTINUATIONS + 1):
+        if have >= spp:
+            break
+        cont = stem + '_' + str(k) + ext
+        if not os.path.isfile(cont):
+            break
+        c = _open_raw(cont)
+        if c.shape[:2] != a.shape[:2]:
+            raise ValueError("%s: a %d x %d continuation of the %d x %d frame %s" % ((cont,) + c.shape[:2] + a.shape[:2] + (fn,)))
+        parts.append(c[:, :, :spp - have])
+        have += parts[-1].shape[2]
+    if have < spp:
+        raise ValueError("%s and its continuation files (%s_1%s, ...) hold %d samples per pixel, fewer than the %d asked for (--spp)"
+                         % (fn, stem, ext, have, spp))
+    return parts, spp
+
+
+def upload_raw(parts, device):
+    """One contiguous (H, W, spp, 104) device tensor from the host parts (each read from disk once), sanitised."""
+    h, w = parts[0].shape[:2]
+    spp = sum(p.shape[2] for p in parts)
+    raw = torch.empty((h, w, spp, 104), device=device, dtype=torch.float32)
+    s0 = 0
+    for p in parts:
+        t = torch.from_numpy(np.array(p, dtype=np.float32, order='C'))
+        if len(parts) == 1:
+            raw.copy_(t)
+        else:
+            raw[:, :, s0:s0 + p.shape[2]] = t.to(device)
+        s0 += p.shape[2]
+    return ops.sanitize_(raw)
+
+
+# ------------------------------------------------------------------------------------------------- one frame
+def denoise_file(interface, fn, output_dir, args, device):
+    """Denoise ``fn`` and write its outputs; returns the dict of phase seconds."""
+    stem = os.path.splitext(os.path.basename(fn))[0]
+    sync = lambda: torch.cuda.synchronize(device)                  # noqa: E731
+    t0 = time.perf_counter()
+    parts, spp = read_raw(fn, args.spp)
+    batch_size = tile_batch_size(spp, args.tile_batch)
+    h, w = parts[0].shape[:2]
+    raw = upload_raw(parts, device)
+    sync()
+    t1 = time.perf_counter()
+    pre = DenoisePreprocessor()
+    kpcn = pre._preprocess_kpcn(raw)
+    llpm = pre._preprocess_llpm(raw)                               # always: has_hit is taken from it
+    del raw
+    sync()
+    t2 = time.perf_counter()
+    times = {}
+    res = denoise_frame(interface, kpcn, llpm, args.use_llpm_buf, batch_size, want_pbuffers=args.save_pbuffer,
+                        patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
+    out, out_path = res[0], (res[3] if args.save_pbuffer else None)
+    os.makedirs(output_dir, exist_ok=True)
+    img = out.cpu().numpy()
+    np.save(os.path.join(output_dir, stem + '_denoised.npy'), img)
+    write_pfm(os.path.join(output_dir, stem + '_denoised.pfm'), img)
+    if args.png:
+        pv_out, pv_ipt = res[-2], res[-1]
+        write_png(os.path.join(output_dir, stem + '_denoised.png'), pv_out.cpu().numpy())
+        write_png(os.path.join(output_dir, stem + '_input.png'), pv_ipt.cpu().numpy())
+    if args.save_pbuffer:
+        if out_path is None:
+            raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
+        p = out_path['diffuse'] if isinstance(out_path, dict) else out_path
+        np.save(os.path.join(output_dir, stem + '_pbuffer.npy'), p.permute(2, 3, 0, 1).cpu().numpy())
+    times.update(upload=t1 - t0, preprocess=t2 - t1, write=time.perf_counter() - t2 - times['network'] - times['finish'])
+    print("%s: %d x %d, %d spp, tiles of %d per call: upload %.3f s, preprocess %.3f s, network %.3f s, finish %.3f s"
+          % (stem, h, w, spp, batch_size, times['upload'], times['preprocess'], times['network'], times['finish']))
+    return times
+
+
+def _model_path(args):
+    name = args.model_name if args.model_name.endswith('.pth') else args.model_name + '.pth'
+    return os.path.join(args.save, name)
+
+
+def load_interface(args, device):
+    """The trained model through ``train_kpcn.init_model`` (``start_epoch`` forced nonzero: it then restores the checkpoint)."""
+    if 'KPCN' not in args.model_name:
+        raise NotImplementedError("denoise: only KPCN models are run; an SBMC / LBMC model needs a base denoiser that the caller must "
+                                  "supply")
+    if args.kpcn_ref:
+        raise NotImplementedError("denoise: KPCN-Ref feeds the clean targets to the network; it cannot denoise a render without "
+                                  "ground truth")
+    if not os.path.isfile(_model_path(args)):
+        raise FileNotFoundError(_model_path(args))
+    if args.start_epoch == 0:
+        args.start_epoch = 1
+    args.model_name = args.model_name[:-4] if args.model_name.endswith('.pth') else args.model_name
+    sizes = {'dncnn_in_size': dncnn_in_size('kpcn', True, False, args.use_llpm_buf, args.pnet_out_size[0]),
+             'pnet_in_size': 36 if args.use_llpm_buf else 0, 'pnet_out_size': args.pnet_out_size[0]}
+    interfaces, _ = train_kpcn.init_model(sizes, args, device)
+    return interfaces[0]
+
+
+def build_parser():
+    p = train_kpcn.build_parser()
+    p.description = "Denoise raw renders of any size with a trained KPCN model (no ground truth needed)."
+    p.epilog = None
+    for a in p._actions:
+        if a.dest == 'desc':
+            a.required = False                     # a training-run label; not needed to denoise
+    p.add_argument('--input', type=str, nargs='+', required=True, help='renderer output files (H, W, S, 104), H and W >= 64')
+    p.add_argument('--output_dir', type=str, required=True, help='where <stem>_denoised.npy / .pfm (and the optional files) go')
+    p.add_argument('--spp', type=int, default=None,
+                   help='samples per pixel to denoise (default: those in the file; more than the file holds are read from '
+                        '<stem>_1.npy, <stem>_2.npy, ... beside it)')
+    p.add_argument('--tile_batch', type=int, default=None,
+                   help='tiles per network call (default: 8 up to 32 spp, 4 up to 64; required above 64)')
+    p.add_argument('--png', action='store_true', help='also write 8-bit tone-mapped <stem>_denoised.png and <stem>_input.png')
+    p.add_argument('--save_pbuffer', action='store_true', help='also write the stitched P-buffer <stem>_pbuffer.npy (H, W, S, C)')
+    return p
+
+
+def check_inputs(args):
+    """Everything that can be refused before the GPU is touched: sample counts, continuation files, the tile batch size."""
+    for fn in args.input:
+        _, spp = read_raw(fn, args.spp)
+        tile_batch_size(spp, args.tile_batch)
+    if args.save_pbuffer and not args.use_llpm_buf:
+        raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
+    return args
+
+
+def main(argv=None):
+    args = check_inputs(train_kpcn.check_args(build_parser().parse_args(argv)))
+    device = torch.device('cuda', args.device_id)
+    torch.cuda.set_device(device)
+    interface = load_interface(args, device)
+    return [denoise_file(interface, fn, args.output_dir, args, device) for fn in args.input]
+
+
+if __name__ == '__main__':
+    main()

@@ -1,6 +1,7 @@
 """The data step on the device: preprocessing and patch assembly (csrc/preprocess.hip), the sampling maps (csrc/sampling_map.hip),
 the buffers and batches of the sample-based denoisers (csrc/sbmc_data.hip), every sample count of a frame from one pass
-(csrc/multi_spp.hip), permutations, and the tile stitching of full-frame inference."""
+(csrc/multi_spp.hip), permutations, the tile stitching of full-frame inference, and the tiles and the closing pass of denoising a
+render of any size (csrc/frame_tiles.hip)."""
 import ctypes
 import math
 
@@ -321,3 +322,75 @@ def stitch_tiles(out, p_buffers, coords, out_rad, out_path=None, patch=128):
                                       ctypes.c_void_p(coords.data_ptr()), b, h, w, _ptr(out_rad), _ptr(oa), _ptr(ob),
                                       _stream()), "stitch_tiles")
     return out_rad, out_path
+
+
+# ---------------------------------------------------------------------------------- denoising a render (csrc/frame_tiles.hip)
+def check_tile_origins(origins, h, w, patch, pad, who="assemble_kpcn_tiles"):
+    """Host check of (B, 2) tile origins (rows, columns) in frame coordinates: every ``patch``-pixel tile lies inside the h x w
+    frame extended by ``pad`` pixels on every side, ``-pad <= o <= dim + pad - patch``."""
+    import numpy as np
+    o = origins.cpu().numpy() if isinstance(origins, torch.Tensor) else np.asarray(origins)
+    if o.size and (int(o.min()) < -pad or int(o[:, 0].max()) > h + pad - patch or int(o[:, 1].max()) > w + pad - patch):
+        raise ValueError("%s: a %d-pixel tile origin lies outside the %dx%d frame extended by %d" % (who, patch, h, w, pad))
+
+
+def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=True):
+    """The inference batch of the KPCN base model -- ``assemble_kpcn_patches`` without ``gt`` and without the ``target_*`` entries --
+    for tiles of ``patch`` pixels at ``origins`` ((B, 2) int32 device tensor of (row, column) in frame coordinates, from ``-pad``
+    upward) of the frame extended by ``pad`` pixels by mirror reflection with the edge repeated (``wcmc_assemble_kpcn_tiles``; bit
+    for bit the batch of the ``np.pad(raw, pad, 'symmetric')`` frame at ``origins + pad``, which is never built).  The origins are
+    data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the table once
+    (checking a device tensor here synchronises)."""
+    _need_cuda(kpcn)
+    if not origins.is_cuda:
+        raise RuntimeError("assemble_kpcn_tiles: origins must be a device tensor")
+    h, w = kpcn.shape[:2]
+    assert kpcn.shape == (h, w, 44) and kpcn.is_contiguous()
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
+    if check_origins:
+        check_tile_origins(origins, h, w, patch, pad)
+    b, s = origins.shape[0], 0
+    if llpm is not None:
+        _need_cuda(llpm)
+        assert llpm.shape[:2] == (h, w) and llpm.shape[3] == 37 and llpm.is_contiguous()
+        s = llpm.shape[2]
+    cin = 35 if llpm is not None else 34
+    shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
+              "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
+              "kpcn_albedo": (b, 3, patch, patch)}
+    if llpm is not None:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    # ONE allocation, the entries are 256-byte aligned views of it (as assemble_kpcn_patches)
+    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
+    flat = torch.empty(sum(sizes.values()), device=kpcn.device, dtype=torch.float32)
+    out, off = {}, 0
+    for k, shp in shapes.items():
+        out[k] = flat[off:off + math.prod(shp)].view(shp)
+        off += sizes[k]
+    check(lib().wcmc_assemble_kpcn_tiles(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad,
+                                         _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
+                                         _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
+                                         _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _stream()), "assemble_kpcn_tiles")
+    return out
+
+
+def finish_frame(out_rad, kpcn, llpm, preview=False):
+    """The closing pass of denoising a frame (``wcmc_finish_frame``): out_rad (3, H, W) stitched radiance, kpcn (H, W, 44),
+    llpm (H, W, S, 37) -> ``(out, ipt, has_hit)``: the noisy input ``ipt`` (H, W, 3) (datasets.py:1234), ``has_hit`` (H, W) fp32 0 / 1
+    (descriptor 24 nonzero in the mean over the S samples, datasets.py:1407-1414) and the composite ``out`` (H, W, 3) = the network's
+    output where a surface was hit, the input elsewhere (test_models.py:231-232).  ``preview=True`` adds ``(preview_out,
+    preview_ipt)``, the (H, W, 3) uint8 images round(255 * tonemap(.)) (test_models.py:24-34, gamma 1/2.2)."""
+    _need_cuda(out_rad, kpcn, llpm)
+    h, w = kpcn.shape[:2]
+    if (tuple(out_rad.shape) != (3, h, w) or tuple(kpcn.shape) != (h, w, 44) or llpm.dim() != 4 or tuple(llpm.shape[:2]) != (h, w)
+            or llpm.shape[3] != 37 or llpm.shape[2] < 1 or not (out_rad.is_contiguous() and kpcn.is_contiguous() and llpm.is_contiguous())):
+        raise ValueError("finish_frame: out_rad should be contiguous (3, H, W), kpcn (H, W, 44) and llpm (H, W, S, 37), got %s, %s, %s"
+                         % (tuple(out_rad.shape), tuple(kpcn.shape), tuple(llpm.shape)))
+    dev = kpcn.device
+    out = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
+    ipt = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
+    has_hit = torch.empty((h, w), device=dev, dtype=torch.float32)
+    pv = [torch.empty((h, w, 3), device=dev, dtype=torch.uint8) for _ in range(2)] if preview else [None, None]
+    check(lib().wcmc_finish_frame(_ptr(out_rad), _ptr(kpcn), _ptr(llpm), h, w, llpm.shape[2], _ptr(out), _ptr(ipt), _ptr(has_hit),
+                                  _ptr(pv[0]), _ptr(pv[1]), _stream()), "finish_frame")
+    return (out, ipt, has_hit, pv[0], pv[1]) if preview else (out, ipt, has_hit)

@@ -61,6 +61,7 @@ class BaseInterface(metaclass=ABCMeta):
 
 _BATCH_KEYS = ('target_total', 'target_diffuse', 'target_specular', 'kpcn_diffuse_in', 'kpcn_specular_in',
                'kpcn_diffuse_buffer', 'kpcn_specular_buffer', 'kpcn_albedo')
+_INFER_KEYS = ('kpcn_diffuse_in', 'kpcn_specular_in', 'kpcn_diffuse_buffer', 'kpcn_specular_buffer', 'kpcn_albedo')
 _OPTIONS = ('m11r11', 'm10r01', 'm11r01', 'm10r11')
 
 
@@ -453,6 +454,20 @@ class KPCNInterface(BaseInterface):
 
         return self._score_validation(batch, out), p_buffers
 
+    def denoise_batch(self, batch):
+        """``validate_batch`` for a batch without targets (``ops.assemble_kpcn_tiles``): the same PathNets, split, assembly and
+        ``dncnn``, nothing scored and ``m_losses`` untouched.  Returns ``(radiance, p_buffers)``."""
+        p_buffers = None
+        new_batch = {k: batch[k] for k in _INFER_KEYS}
+        if self.use_llpm_buf:
+            batch.pop('_wcmc_paths_nhwc', None)
+            p_buffers = self._manifold_forward(batch)
+            _, p_buffers = self._split(p_buffers, train=False)
+            # (`_assemble` without the target_* entries)
+            new_batch['kpcn_diffuse_in'] = _ops.pbuffer_cat(batch['kpcn_diffuse_in'], p_buffers['diffuse'])
+            new_batch['kpcn_specular_in'] = _ops.pbuffer_cat(batch['kpcn_specular_in'], p_buffers['specular'])
+        return self._regress_forward(new_batch)['radiance'], p_buffers
+
     def _score_validation(self, batch, out):
         """interfaces.py:296-300: running sum of the test loss (RelativeMSE) of the denoised radiance against the
         cropped target; the accumulator moves to the loss's device on first use."""
@@ -517,6 +532,10 @@ class KPCNRefInterface(KPCNInterface):
         batch = self._with_targets(batch)
         out = self._regress_forward(batch)
         return self._score_validation(batch, out), None
+
+    def denoise_batch(self, batch):
+        raise NotImplementedError("KPCNRefInterface feeds the clean per-branch targets to the network (its inputs are extended by "
+                                  "target_diffuse / target_specular): it cannot denoise a render that has no ground truth")
 
 
 class KPCNPreInterface(KPCNInterface):
