@@ -527,6 +527,18 @@ size_t wcmc_preprocess_kpcn_workspace_bytes(int h, int w);
 int wcmc_preprocess_kpcn(const float* raw, int h, int w, int s, int C, int max_depth, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 int wcmc_gradients(const float* buf, int h, int w, int c, float* out, void* stream);
+/* wcmc_preprocess_kpcn in row bands (support/staging.py streams a frame that never lies whole on the device): `out` (h, w, 44) and the
+ * workspace (wcmc_preprocess_kpcn_workspace_bytes(h, w): [mean depth, depth variance] per pixel, then the image maximum of the mean
+ * depth) belong to the whole frame.  _begin zeroes the maximum slot; _rows runs pass 1 (the per-pixel statistics; the maximum by an
+ * atomic on that slot) on frame rows [row0, row0 + rows) from raw_band (rows, w, s, C), choosing among the three statistics kernels
+ * by the band's own alignment; _end runs pass 2 (depth normalisation, backward differences) over the frame once every row has been
+ * through _rows.  Any partition of [0, h) gives wcmc_preprocess_kpcn's result bit for bit; wcmc_preprocess_kpcn is
+ * _begin + _rows(0, h) + _end.  All on one stream, or ordered by the caller.  Null pointers and rows outside the frame (row0 < 0,
+ * rows < 1, row0 + rows > h) are WCMC_ERR_BAD_ARG, a short workspace WCMC_ERR_WORKSPACE, before any launch. */
+int wcmc_preprocess_kpcn_begin(void* workspace, size_t workspace_bytes, int h, int w, void* stream);
+int wcmc_preprocess_kpcn_rows(const float* raw_band, int h, int w, int row0, int rows, int s, int C, int max_depth, float* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int wcmc_preprocess_kpcn_end(float* out, void* workspace, size_t workspace_bytes, int h, int w, int s, void* stream);
 
 /* Batch assembly for the KPCN base model (DenoiseDataset.__getitem__ + _sample_patches + _transpose,
  * support/datasets.py:795-840,1026-1146): crops B windows of P x P pixels at origins[b] = (row, column) out of the

@@ -105,6 +105,9 @@ SIGNATURES = {
     "wcmc_preprocess_llpm": (I, [P, L, I, I, P, P]),
     "wcmc_preprocess_kpcn_workspace_bytes": (Z, [I, I]),
     "wcmc_preprocess_kpcn": (I, [P, I, I, I, I, I, P, P, Z, P]),
+    "wcmc_preprocess_kpcn_begin": (I, [P, Z, I, I, P]),
+    "wcmc_preprocess_kpcn_rows": (I, [P, I, I, I, I, I, I, I, P, P, Z, P]),
+    "wcmc_preprocess_kpcn_end": (I, [P, P, Z, I, I, I, P]),
     "wcmc_gradients": (I, [P, I, I, I, P, P]),
     "wcmc_assemble_kpcn_patches": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "wcmc_reflect_index": (I, [I, I]),

@@ -93,7 +93,10 @@ __device__ __forceinline__ void pp_mean_var(const float* __restrict__ px, int s,
 
 // pass 1: everything that needs only the pixel's own samples; depth stays raw in the workspace
 __global__ __launch_bounds__(256) void pp_kpcn_stats_kernel(const float* __restrict__ raw, float* __restrict__ out,
-                                                            float* __restrict__ ws, int64_t npix, int s, int C, PPMap m) {
+                                                            float* __restrict__ ws, int* __restrict__ maxslot, int64_t npix,
+                                                            int s, int C, PPMap m) {
+  // raw / out / ws start at the first of the npix pixels this launch covers (a whole frame or a band of its rows); maxslot is the
+  // frame's maximum slot, wherever the band lies
   const float eps = 0.00316f;
   float bmax = 0.f;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_kernel(const float* __restr
   bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1) bmax = fmaxf(bmax, __shfl_xor(bmax, off, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(ws + 2 * npix), __float_as_int(bmax));
+  if ((threadIdx.x & 63) == 0) atomicMax(maxslot, __float_as_int(bmax));
 }
 
 // pass 1, one lane per (pixel, sample) for power-of-two spp <= 64: the s lanes of a pixel sit side by side, so a
@@ -141,8 +144,8 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_kernel(const float* __restr
 // (the per-pixel form above walks each pixel's records from a single lane, 3.3 KB apart across the wave).
 template <bool VEC>
 __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* __restrict__ raw, float* __restrict__ out,
-                                                                  float* __restrict__ ws, int64_t npix, int s, int C,
-                                                                  PPMap m) {
+                                                                  float* __restrict__ ws, int* __restrict__ maxslot,
+                                                                  int64_t npix, int s, int C, PPMap m) {
   const float spp = (float)s;
   const int ppw = 64 / s;                                       // pixels per wave
   const int lane = threadIdx.x & 63, k = lane & (s - 1), pl = lane / s;
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(256) void pp_kpcn_stats_lanes_kernel(const float* _
   bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1) bmax = fmaxf(bmax, __shfl_xor(bmax, off, 64));
-  if (lane == 0) atomicMax(reinterpret_cast<int*>(ws + 2 * npix), __float_as_int(bmax));
+  if (lane == 0) atomicMax(maxslot, __float_as_int(bmax));
 }
 
 // pass 2 (data_step.h: pp_kpcn_finish)
@@ -215,31 +218,75 @@ extern "C" size_t wcmc_preprocess_kpcn_workspace_bytes(int h, int w) {
   return ((size_t)2 * h * w + 4) * sizeof(float);
 }
 
+// The frame in row bands (support/staging.py): begin zeroes the maximum slot, rows runs pass 1 on the band's rows -- everything pass 1
+// writes is the pixel's own, and the maximum is an atomic on one slot, so any partition of the rows gives the whole frame's bits --
+// and end runs pass 2, the only place where pixels meet (the maximum and the backward differences).
+static int pp_kpcn_frame_args(const char* who, const void* out, const void* workspace, size_t workspace_bytes, int h, int w) {
+  WCMC_REQUIRE(out && workspace, WCMC_ERR_BAD_ARG, "%s: null pointer", who);
+  WCMC_REQUIRE(h > 0 && w > 0, WCMC_ERR_BAD_ARG, "%s: the frame (%d x %d) must be positive", who, h, w);
+  WCMC_REQUIRE(workspace_bytes >= wcmc_preprocess_kpcn_workspace_bytes(h, w), WCMC_ERR_WORKSPACE,
+               "%s: workspace too small (%zu bytes, the %d x %d frame needs %zu)", who, workspace_bytes, h, w,
+               wcmc_preprocess_kpcn_workspace_bytes(h, w));
+  return WCMC_OK;
+}
+
+extern "C" int wcmc_preprocess_kpcn_begin(void* workspace, size_t workspace_bytes, int h, int w, void* stream) {
+  int rc = pp_kpcn_frame_args("preprocess_kpcn_begin", workspace, workspace, workspace_bytes, h, w);
+  if (rc) return rc;
+  if (hipMemsetAsync((float*)workspace + 2 * (int64_t)h * w, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) {
+    set_error("preprocess_kpcn_begin: memset failed");
+    return WCMC_ERR_LAUNCH;
+  }
+  return WCMC_OK;
+}
+
+extern "C" int wcmc_preprocess_kpcn_rows(const float* raw_band, int h, int w, int row0, int rows, int s, int C, int max_depth,
+                                         float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  WCMC_REQUIRE(raw_band, WCMC_ERR_BAD_ARG, "preprocess_kpcn_rows: null pointer");
+  int rc = pp_kpcn_frame_args("preprocess_kpcn_rows", out, workspace, workspace_bytes, h, w);
+  if (rc) return rc;
+  WCMC_REQUIRE(s > 0 && max_depth >= 0 && C >= 38 + 11 * (max_depth + 1), WCMC_ERR_BAD_ARG,
+               "preprocess_kpcn_rows: bad argument (s = %d, raw needs >= 38 + 11*(max_depth+1) channels, got %d)", s, C);
+  WCMC_REQUIRE(row0 >= 0 && rows >= 1 && rows <= h - row0, WCMC_ERR_BAD_ARG,
+               "preprocess_kpcn_rows: rows [%d, %d + %d) are not rows of the %d-row frame", row0, row0, rows, h);
+  const PPMap m = pp_map(max_depth);
+  const int64_t npix = (int64_t)rows * w, p0 = (int64_t)row0 * w;
+  float* ws = (float*)workspace;
+  int* maxslot = reinterpret_cast<int*>(ws + 2 * (int64_t)h * w);
+  float* o = out + p0 * KP_C;
+  float* wsb = ws + 2 * p0;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = pp_kpcn_vec_ok(raw_band, C, m);
+  if (s <= 64 && (s & (s - 1)) == 0 && vec)
+    hipLaunchKernelGGL(pp_kpcn_stats_lanes_kernel<true>, dim3(pp_grid(npix * s)), dim3(256), 0, st, raw_band, o, wsb, maxslot, npix, s, C, m);
+  else if (s <= 64 && (s & (s - 1)) == 0)
+    hipLaunchKernelGGL(pp_kpcn_stats_lanes_kernel<false>, dim3(pp_grid(npix * s)), dim3(256), 0, st, raw_band, o, wsb, maxslot, npix, s, C, m);
+  else
+    hipLaunchKernelGGL(pp_kpcn_stats_kernel, dim3(pp_grid(npix)), dim3(256), 0, st, raw_band, o, wsb, maxslot, npix, s, C, m);
+  return check_launch("preprocess_kpcn_rows(stats)");
+}
+
+extern "C" int wcmc_preprocess_kpcn_end(float* out, void* workspace, size_t workspace_bytes, int h, int w, int s, void* stream) {
+  int rc = pp_kpcn_frame_args("preprocess_kpcn_end", out, workspace, workspace_bytes, h, w);
+  if (rc) return rc;
+  WCMC_REQUIRE(s > 0, WCMC_ERR_BAD_ARG, "preprocess_kpcn_end: s = %d must be positive", s);
+  hipLaunchKernelGGL(pp_kpcn_finish_kernel, dim3(pp_grid((int64_t)h * w * KP_C)), dim3(256), 0, (hipStream_t)stream, out,
+                     (const float*)workspace, h, w, s);
+  return check_launch("preprocess_kpcn_end(finish)");
+}
+
 extern "C" int wcmc_preprocess_kpcn(const float* raw, int h, int w, int s, int C, int max_depth, float* out,
                                     void* workspace, size_t workspace_bytes, void* stream) {
   WCMC_REQUIRE(raw && out && workspace && h > 0 && w > 0 && s > 0 && max_depth >= 0 && C >= 38 + 11 * (max_depth + 1),
                WCMC_ERR_BAD_ARG, "preprocess_kpcn: bad argument");
   WCMC_REQUIRE(workspace_bytes >= wcmc_preprocess_kpcn_workspace_bytes(h, w), WCMC_ERR_WORKSPACE,
                "preprocess_kpcn: workspace too small");
-  const PPMap m = pp_map(max_depth);
-  const int64_t npix = (int64_t)h * w;
-  float* ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws + 2 * npix, 0, sizeof(float), st) != hipSuccess) {
-    set_error("preprocess_kpcn: memset failed");
-    return WCMC_ERR_LAUNCH;
-  }
-  const bool vec = pp_kpcn_vec_ok(raw, C, m);
-  if (s <= 64 && (s & (s - 1)) == 0 && vec)
-    hipLaunchKernelGGL(pp_kpcn_stats_lanes_kernel<true>, dim3(pp_grid(npix * s)), dim3(256), 0, st, raw, out, ws, npix, s, C, m);
-  else if (s <= 64 && (s & (s - 1)) == 0)
-    hipLaunchKernelGGL(pp_kpcn_stats_lanes_kernel<false>, dim3(pp_grid(npix * s)), dim3(256), 0, st, raw, out, ws, npix, s, C, m);
-  else
-    hipLaunchKernelGGL(pp_kpcn_stats_kernel, dim3(pp_grid(npix)), dim3(256), 0, st, raw, out, ws, npix, s, C, m);
-  int rc = check_launch("preprocess_kpcn(stats)");
+  // the whole frame as one band: the same memset, the same two launches with the same grids as before the band entry points
+  int rc = wcmc_preprocess_kpcn_begin(workspace, workspace_bytes, h, w, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(pp_kpcn_finish_kernel, dim3(pp_grid(npix * KP_C)), dim3(256), 0, st, out, ws, h, w, s);
-  return check_launch("preprocess_kpcn(finish)");
+  rc = wcmc_preprocess_kpcn_rows(raw, h, w, 0, h, s, C, max_depth, out, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  return wcmc_preprocess_kpcn_end(out, workspace, workspace_bytes, h, w, s, stream);
 }
 
 // ------------------------------------------------------------------ patch batch assembly (datasets.py:1026-1146)

@@ -1,13 +1,15 @@
 """Denoise raw renders of any size with a trained KPCN model: no ground truth, no offline files, every pixel.
 
     python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
-        [--spp N] [--tile_batch B] [--png] [--save_pbuffer] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
+        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
 
 Per input file (renderer output (H, W, S, 104), H and W at least 64): the first ``--spp`` samples (default: what the file holds; a
-file that holds fewer is continued by ``<stem>_1.npy``, ``<stem>_2.npy``, ... beside it) are uploaded once, sanitised and
-preprocessed on the device; ``support.inference.denoise_frame`` runs the network over mirror-extended tiles and composites the
-result; ``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the
-result and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  The model flags are those of
+file that holds fewer is continued by ``<stem>_1.npy``, ``<stem>_2.npy``, ... beside it) are streamed to the device in row bands,
+sanitised and preprocessed there band by band (``support.staging.FrameStreamer``: the raw frame never lies whole in host or device
+memory, and the next file's bands cross while this one's network runs; ``--band_rows`` bounds the pinned memory);
+``support.inference.denoise_frame`` runs the network over mirror-extended tiles and composites the result;
+``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the result
+and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  The model flags are those of
 ``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  Only the KPCN models are run here (SBMC / LBMC need the
 caller's base denoiser, as in ``wcmc_amd.evaluate``).  One line per frame reports the seconds of each phase.
 """
@@ -20,8 +22,9 @@ import numpy as np
 import torch
 
 from . import ops, train_kpcn
-from .support.datasets import MAX_CONTINUATIONS, DenoisePreprocessor, dncnn_in_size
+from .support.datasets import MAX_CONTINUATIONS, dncnn_in_size
 from .support.inference import denoise_frame
+from .support.staging import FrameStreamer
 
 PATCH_SIZE, PAD_SIZE = 128, 32
 
@@ -105,7 +108,8 @@ def read_raw(fn, spp=None):
 
 
 def upload_raw(parts, device):
-    """One contiguous (H, W, spp, 104) device tensor from the host parts (each read from disk once), sanitised."""
+    """One contiguous (H, W, spp, 104) device tensor from the host parts (each read from disk once), sanitised.  The whole-frame
+    route: ``support.staging.FrameStreamer`` is what the command runs, and this is what its tests hold it to."""
     h, w = parts[0].shape[:2]
     spp = sum(p.shape[2] for p in parts)
     raw = torch.empty((h, w, spp, 104), device=device, dtype=torch.float32)
@@ -121,23 +125,32 @@ def upload_raw(parts, device):
 
 
 # ------------------------------------------------------------------------------------------------- one frame
-def denoise_file(interface, fn, output_dir, args, device):
-    """Denoise ``fn`` and write its outputs; returns the dict of phase seconds."""
+def denoise_file(interface, fn, output_dir, args, device, frames=None):
+    """Denoise ``fn`` and write its outputs; returns the dict of phase seconds.  ``frames``: a ``FrameStreamer`` whose next frame is
+    ``fn`` (``main``: one streamer over all the inputs, so that the next file is prefetched); None: one for ``fn`` alone.
+    'upload' is the host's wait for the frame's buffers -- after the first frame of a sequence, what the prefetch did not hide --
+    and 'preprocess' the finish pass of the preprocessing."""
     stem = os.path.splitext(os.path.basename(fn))[0]
-    sync = lambda: torch.cuda.synchronize(device)                  # noqa: E731
+    own = frames is None
     t0 = time.perf_counter()
-    parts, spp = read_raw(fn, args.spp)
-    batch_size = tile_batch_size(spp, args.tile_batch)
-    h, w = parts[0].shape[:2]
-    raw = upload_raw(parts, device)
-    sync()
+    if own:
+        frames = FrameStreamer([fn], args.spp, device, band_rows=getattr(args, 'band_rows', None))
+    try:
+        kpcn, llpm = next(frames)
+        ev0, ev1 = frames.finish_events
+        ev1.synchronize()
+    finally:
+        if own:
+            frames.close()
+    return denoise_buffers(interface, stem, kpcn, llpm, output_dir, args, time.perf_counter() - t0, ev0.elapsed_time(ev1) * 1e-3)
+
+
+def denoise_buffers(interface, stem, kpcn, llpm, output_dir, args, upload=0.0, preprocess=0.0):
+    """Denoise the frame from its device buffers ``kpcn`` (H, W, 44) and ``llpm`` (H, W, S, 37), ready on the current stream, and write
+    the outputs of ``stem``; returns the dict of phase seconds, with ``upload`` and ``preprocess`` as the caller measured them."""
     t1 = time.perf_counter()
-    pre = DenoisePreprocessor()
-    kpcn = pre._preprocess_kpcn(raw)
-    llpm = pre._preprocess_llpm(raw)                               # always: has_hit is taken from it
-    del raw
-    sync()
-    t2 = time.perf_counter()
+    h, w, spp = llpm.shape[:3]
+    batch_size = tile_batch_size(spp, args.tile_batch)
     times = {}
     res = denoise_frame(interface, kpcn, llpm, args.use_llpm_buf, batch_size, want_pbuffers=args.save_pbuffer,
                         patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
@@ -155,7 +168,7 @@ def denoise_file(interface, fn, output_dir, args, device):
             raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
         p = out_path['diffuse'] if isinstance(out_path, dict) else out_path
         np.save(os.path.join(output_dir, stem + '_pbuffer.npy'), p.permute(2, 3, 0, 1).cpu().numpy())
-    times.update(upload=t1 - t0, preprocess=t2 - t1, write=time.perf_counter() - t2 - times['network'] - times['finish'])
+    times.update(upload=upload, preprocess=preprocess, write=time.perf_counter() - t1 - times['network'] - times['finish'])
     print("%s: %d x %d, %d spp, tiles of %d per call: upload %.3f s, preprocess %.3f s, network %.3f s, finish %.3f s"
           % (stem, h, w, spp, batch_size, times['upload'], times['preprocess'], times['network'], times['finish']))
     return times
@@ -199,13 +212,18 @@ def build_parser():
                         '<stem>_1.npy, <stem>_2.npy, ... beside it)')
     p.add_argument('--tile_batch', type=int, default=None,
                    help='tiles per network call (default: 8 up to 32 spp, 4 up to 64; required above 64)')
+    p.add_argument('--band_rows', type=int, default=None,
+                   help='rows of the frame per band of the streamed upload (default: bands of about 64 MiB); a memory control: six '
+                        'bands are pinned on the host, one lies on the device, and the result does not depend on it')
     p.add_argument('--png', action='store_true', help='also write 8-bit tone-mapped <stem>_denoised.png and <stem>_input.png')
     p.add_argument('--save_pbuffer', action='store_true', help='also write the stitched P-buffer <stem>_pbuffer.npy (H, W, S, C)')
     return p
 
 
 def check_inputs(args):
-    """Everything that can be refused before the GPU is touched: sample counts, continuation files, the tile batch size."""
+    """Everything that can be refused before the GPU is touched: sample counts, continuation files, the tile batch size, the band."""
+    if getattr(args, 'band_rows', None) is not None and args.band_rows < 1:
+        raise ValueError("--band_rows should be at least 1, got %d" % args.band_rows)
     for fn in args.input:
         _, spp = read_raw(fn, args.spp)
         tile_batch_size(spp, args.tile_batch)
@@ -219,7 +237,11 @@ def main(argv=None):
     device = torch.device('cuda', args.device_id)
     torch.cuda.set_device(device)
     interface = load_interface(args, device)
-    return [denoise_file(interface, fn, args.output_dir, args, device) for fn in args.input]
+    frames = FrameStreamer(args.input, args.spp, device, band_rows=args.band_rows)
+    try:
+        return [denoise_file(interface, fn, args.output_dir, args, device, frames=frames) for fn in args.input]
+    finally:
+        frames.close()
 
 
 if __name__ == '__main__':

@@ -165,6 +165,7 @@ from .manifold import (_FeatureMSE, _GRS, grs_loss, feature_mse)  # noqa: E402,F
 from .optim import (clip_grad_norm_, clip_adam_, clip_adam_hyper, clip_adam_dev_, step_guard_, step_guard_local_,  # noqa: E402,F401
                     step_guard_global_)
 from .data import (_need_dense, preprocess_llpm, preprocess_kpcn, assemble_kpcn_patches, gradients, reflect_index,  # noqa: E402,F401
+                   preprocess_kpcn_begin, preprocess_kpcn_rows, preprocess_kpcn_end,
                    importance_map, sampling_prob, sanitize_, random_permutation, random_permutation_dev, step_counter_advance,
                    permutation_key, check_tile_coords, stitch_tiles, preprocess_sbmc, check_patch_origins, sample_feature_size,
                    assemble_sample_patches, preprocess_kpcn_prefix, check_tile_origins, assemble_kpcn_tiles, finish_frame)

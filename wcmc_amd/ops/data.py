@@ -18,11 +18,19 @@ def _need_dense(t, ndim):
                            "layout (got %s %s %s); there is no CPU path" % (t.device, t.dtype, tuple(t.shape)))
 
 
-def preprocess_llpm(sample, max_depth=5):
-    """``DenoiseDataset._preprocess_llpm`` (datasets.py:302-361): raw (h,w,s,C) -> (h,w,s,37)."""
+def preprocess_llpm(sample, max_depth=5, out=None):
+    """``DenoiseDataset._preprocess_llpm`` (datasets.py:302-361): raw (h,w,s,C) -> (h,w,s,37).  ``out``: a contiguous (h,w,s,37)
+    tensor to write into -- a row slice of a frame's buffer when ``sample`` is a band of its rows (the function is per sample)."""
     _need_dense(sample, 4)
     h, w, s, c = sample.shape
-    out = torch.empty((h, w, s, 7 + 5 * (max_depth + 1)), device=sample.device, dtype=torch.float32)
+    oc = 7 + 5 * (max_depth + 1)
+    if out is None:
+        out = torch.empty((h, w, s, oc), device=sample.device, dtype=torch.float32)
+    else:
+        _need_dense(out, 4)
+        if tuple(out.shape) != (h, w, s, oc) or out.device != sample.device:
+            raise ValueError("preprocess_llpm: out should be (%d, %d, %d, %d) on %s, got %s on %s"
+                             % (h, w, s, oc, sample.device, tuple(out.shape), out.device))
     check(lib().wcmc_preprocess_llpm(_ptr(sample), h * w * s, c, max_depth, _ptr(out), _stream()), "preprocess_llpm")
     return out
 
@@ -36,6 +44,50 @@ def preprocess_kpcn(sample, max_depth=5):
     ws = torch.empty((nbytes + 3) // 4, device=sample.device, dtype=torch.float32)
     check(lib().wcmc_preprocess_kpcn(_ptr(sample), h, w, s, c, max_depth, _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
           "preprocess_kpcn")
+    return out
+
+
+def preprocess_kpcn_begin(h, w, device):
+    """Start ``preprocess_kpcn`` of an (h, w) frame that arrives in row bands: ``(out (h,w,44), workspace)``, the workspace's maximum
+    slot zeroed on the current stream.  Every row then goes through ``preprocess_kpcn_rows`` once, in any partition and order, and
+    ``preprocess_kpcn_end`` closes the frame -- bit for bit ``preprocess_kpcn`` of the whole frame.  One stream, or the caller orders."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("preprocess_kpcn_begin: the frame (%d x %d) must be positive" % (h, w))
+    out = torch.empty((h, w, 44), device=device, dtype=torch.float32)
+    nbytes = lib().wcmc_preprocess_kpcn_workspace_bytes(h, w)
+    ws = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+    check(lib().wcmc_preprocess_kpcn_begin(_ptr(ws), ws.numel() * 4, h, w, _stream()), "preprocess_kpcn_begin")
+    return out, ws
+
+
+def _need_kpcn_frame(who, out, ws):
+    _need_dense(out, 3)
+    if out.shape[2] != 44 or not ws.is_cuda or ws.dtype != torch.float32 or not ws.is_contiguous() or ws.device != out.device:
+        raise ValueError("%s: out should be (h, w, 44) and the workspace the fp32 tensor of preprocess_kpcn_begin on its device, got %s "
+                         "and %s %s" % (who, tuple(out.shape), ws.dtype, ws.device))
+
+
+def preprocess_kpcn_rows(band, row0, out, ws, max_depth=5):
+    """Pass 1 of ``preprocess_kpcn`` on frame rows ``[row0, row0 + rows)``: ``band`` is their raw samples (rows, w, s, C), ``out`` and
+    ``ws`` the frame's, from ``preprocess_kpcn_begin``.  A band that does not start on a 16-byte boundary takes the scalar loads."""
+    _need_dense(band, 4)
+    _need_kpcn_frame("preprocess_kpcn_rows", out, ws)
+    rows, w, s, c = band.shape
+    h = out.shape[0]
+    if out.shape[1] != w or band.device != out.device:
+        raise ValueError("preprocess_kpcn_rows: a band %d pixels wide on %s for a frame %d wide on %s" % (w, band.device, out.shape[1], out.device))
+    check(lib().wcmc_preprocess_kpcn_rows(_ptr(band), h, w, int(row0), rows, s, c, max_depth, _ptr(out), _ptr(ws), ws.numel() * 4,
+                                          _stream()), "preprocess_kpcn_rows")
+    return out
+
+
+def preprocess_kpcn_end(out, ws, s):
+    """Pass 2 of ``preprocess_kpcn`` over the frame whose rows have all been through ``preprocess_kpcn_rows`` at ``s`` samples per
+    pixel: depth normalised by the frame's maximum, backward differences.  Returns ``out``, now final."""
+    _need_kpcn_frame("preprocess_kpcn_end", out, ws)
+    h, w = out.shape[:2]
+    check(lib().wcmc_preprocess_kpcn_end(_ptr(out), _ptr(ws), ws.numel() * 4, h, w, int(s), _stream()), "preprocess_kpcn_end")
     return out
 
 
