@@ -259,6 +259,23 @@ int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int p
                     float* db1, void* workspace, size_t workspace_bytes, void* stream);
 size_t wcmc_conv2d_igemm_colsum_elems(int N, int Ho, int Wo, int Cout);
 int wcmc_colsum_finish(const float* partial, int N, int Ho, int Wo, int Cout, float* db, void* stream);
+/* Which kernel a launch WOULD run, from the code that launches, without touching the device (no GPU needed).  Each writes two
+ * NUL-terminated strings into caller buffers of `len` bytes and returns 0: cls = the profiler class (conv_pw | conv_halo3[_x2] |
+ * conv_halo64_pt3|pt4[_x2|_x1|_h1] | conv_halo64_cs32 | conv_halo7 | conv_igemm; conv_wgrad_rows | conv_wgrad -- a class that
+ * stands for ONE kernel instance is given to that instance only, any other kernel gets conv_igemm / conv_wgrad) and kernel = the
+ * instance as rocprofv3 prints it without "wcmc::", every template argument written out.  Arguments the launch would refuse (and
+ * buffers too short) return the launch's error code, message in wcmc_last_error -- those that can be told from these scalars: the
+ * launch also refuses an fp32 output with a gate MASK or a mask output, and misaligned or missing buffers, which the query is not
+ * told about.  (Both launches check the shape first: of several bad arguments, WCMC_ERR_BAD_ARG for the shape is the one reported,
+ * before WCMC_ERR_ALIGNMENT and WCMC_ERR_WORKSPACE.)  The debug library follows its A/B switches.
+ * wcmc_conv2d_launch_plan_bf16x3: wcmc_conv2d_igemm_bf16x3 (split_out: y_split given, else y with the strides ysn / ysh / ysw;
+ * gate_tensor: gate_split given) or, with out_f16 != 0, wcmc_conv2d_out_f16.  wcmc_conv2d_wgrad_launch_plan_bf16x3: the GEMM
+ * launch (phase 0 or 1) of wcmc_conv2d_wgrad_bf16x3. */
+int wcmc_conv2d_launch_plan_bf16x3(int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms, int split_out,
+                                   int64_t ysn, int64_t ysh, int64_t ysw, int gate_tensor, int out_f16,
+                                   char* cls, char* kernel, size_t len);
+int wcmc_conv2d_wgrad_launch_plan_bf16x3(int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms,
+                                         char* cls, char* kernel, size_t len);
 size_t wcmc_conv2d_wgrad_bf16x3_workspace_bytes(int N, int Ho, int Wo, int Cout, int Cin, int ks);
 /* phase: 0 = everything; 1 = the split-K GEMM into the workspace only; 2 = the slab reduction and
  * bias gradient only (1 then 2 == 0; lets a profiler bracket the GEMM launch alone).

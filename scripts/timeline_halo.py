@@ -1,7 +1,7 @@
 """Wall-clock timeline of the halo-resident 5x5 kernel's workgroups (s_memrealtime stamps of the debug build):
    make -C wcmc_amd/csrc debug; WCMC_DEBUG_LIB=1 WCMC_DEBUG_ABLATE=64 python3 scripts/timeline_halo.py [h ...]
 Per workgroup: entry -> stage loop -> end of loop -> exit, and the CU it ran on; prints the round structure of a launch."""
-import sys, os
+import re, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from wcmc_amd import ops as o
@@ -19,7 +19,10 @@ for h in [int(a) for a in sys.argv[1:] if a != "--unet"] or [124, 116, 100]:
         y, part = o.conv2d_x_raw(xs, (n, cin, h, h), wp, b, cout, ks, pad, "relu", out_split=True, colsum=True)
     torch.cuda.synchronize()
     ho = h + 2 * pad - ks + 1
-    th = 8 if unet else 16 if os.environ.get("WCMC_HALO64", "1") != "0" else 8      # conv_halo64: 16x16 tiles; conv_halo<7,8,16>: 8x16
+    # tile height of the kernel the library's launch plan names: conv_halo64<NT, NB, PT, ..>: 4 * PT rows; conv_halo<NT, TH, ..>: TH; conv_halo3: 8
+    ker = o.conv_launch_plan(n, h, h, cin, cout, ks, pad)[1]
+    targs = [int(a) for a in re.findall(r"\d+", ker[ker.index("<"):])]
+    th = 4 * targs[2] if ker.startswith("conv_halo64_") else targs[1] if ker.startswith("conv_halo_") else 8
     tiles, nw = n * ((ho + th - 1) // th) * ((ho + 15) // 16), (1 if unet else 4)     # (64 couts: room for one wave's record per tile)
     st = part.cpu().numpy().view(np.uint64)[: tiles * nw * 14].reshape(tiles, nw, 14)
     rt = st[:, :, 6:13].astype(np.float64) * 0.01          # us: entry, loop start, loop end, E0, E1, E2, exit

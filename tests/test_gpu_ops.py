@@ -225,6 +225,8 @@ def test_gate_from_bit_mask_equals_gate_from_tensor(case):
     assert torch.equal(bits[:, :cout].bool(), want) and float((yd > 0).float().mean()) > 0.2
     dys = o.split_raw(o.to_nhwc_raw(gen(n, 48, ho, wo, seed=73).to(DEV)))
     w2t = o._pack_x(gen(48, cout, ks, ks, seed=74, scale=0.1).to(DEV), 1)
+    # (a launch gated by a TENSOR never runs the pointwise kernel, x_plan_pw; the mask-gated one may)
+    assert o.conv_launch_plan(n, ho, wo, 48, cout, ks, ks - 1 - pad, gate=True)[0] != "conv_pw"
     for act in ("relu", "leaky_relu"):
         a = o.conv2d_x_raw(dys, (n, 48, ho, wo), w2t, None, cout, ks, ks - 1 - pad, "linear", out_split=True,
                            gate=y, gate_act=act) if pad == ks // 2 or ks == 1 else None
@@ -318,9 +320,14 @@ def test_halo64_mixed_tile_heights_variant_is_bit_identical_to_the_pure_tilings(
     for sw in ("2", "0"):
         monkeypatch.setenv("WCMC_HALO64_MIX", sw)
         monkeypatch.setenv("WCMC_HALO64_STRIP", "1" if sw == "2" else "0")      # (the transposed 12-wide strip of the widths likewise)
+        got["kernel " + sw] = o.conv_launch_plan(n, h, w, cin, cout, ks, pad)[1]
         y, part, mask = o.conv2d_x_raw(xs, (n, cin, h, w), o._pack_x(wt, 0), b, cout, ks, pad, "relu", out_split=True, colsum=True, mask_out=True)
         yf = o.conv2d_x_raw(xs, (n, cin, h, w), o._pack_x(wt, 3), b, cout, ks, pad, "linear", out_split=False, terms=2)
         got[sw] = (y.clone(), mask.clone(), yf.clone(), o.colsum_finish_raw(part, (n, cout, ho, wo)))
+    # the launch plan follows the switch: a height that 16 does not divide but 16s and 12s cover exactly runs the 16-row instance
+    # (PT = 4) with the mix, whatever the pure tiling was; any other height keeps its instance
+    mixed = ho % 16 != 0 and any((ho - 12 * k) % 16 == 0 for k in range(1, (ho - 1) // 12 + 1))
+    assert got["kernel 2"].split(", ")[2] == "4" if mixed else got["kernel 2"] == got["kernel 0"], (got["kernel 2"], got["kernel 0"])
     a, bb = got["2"], got["0"]
     assert torch.equal(a[0], bb[0]) and torch.equal(a[1], bb[1]) and torch.equal(a[2], bb[2])
     assert rel_err(a[3], bb[3]) < 2e-6
@@ -379,12 +386,14 @@ def test_unet3x3_kernel_variant_equals_the_kernel_it_replaced(case, monkeypatch)
     got = {}
     for sw in ("1", "0"):
         monkeypatch.setenv("WCMC_HALO3", sw)
+        got["kernel " + sw] = o.conv_launch_plan(n, h, w, cin, cout, 3, 1)[1]
         y, mask = o.conv2d_x_raw(xs, dims, wp0, b, cout, 3, 1, "relu", out_split=True, mask_out=True)
         yf = o.conv2d_x_raw(xs, dims, wp0, b, cout, 3, 1, "leaky_relu", out_split=False)
         dx, part = o.conv2d_x_raw(dys, (n, cout, h, w), wp2, None, cin, 3, 1, "linear", out_split=True, gate_mask=gmask, gate_act="relu",
                                     colsum=True, terms=2)
         got[sw] = (o.unsplit_debug(y, n, cout, h, w), mask.clone(), yf.clone(),
                    o.unsplit_debug(dx, n, cin, h, w), o.colsum_finish_raw(part, (n, cin, h, w)))
+    assert got["kernel 1"] == "conv_halo3_bf16x3_kernel<2, 2, 2, 0>" and got["kernel 0"].startswith("conv_halo_bf16x3_kernel<"), (got["kernel 1"], got["kernel 0"])
     a, bb = got["1"], got["0"]
     # (a split output resolves 2^-17 of an element: two fp32 sums an ulp apart may round its lo plane apart)
     for i, what, tol in ((0, "forward", 1.6e-5), (2, "forward, fp32 view", 2e-6), (3, "data gradient", 1.6e-5), (4, "column sums (of the split values, with cancellation)", 1e-5)):
@@ -414,6 +423,7 @@ def test_weight_gradient_with_many_slabs_against_fp64(case, monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+        got["kernel of the " + name] = o.wgrad_launch_plan(n, h, w, cin, cout, ks, pad, 3)[1]
         dw, db = o.conv2d_wgrad_x_raw(xs, (n, cin, h, w), dys, cout, ks, pad, (cout, cin, ks, ks), terms=3)
         dw2, db2 = o.conv2d_wgrad_x_raw(xs, (n, cin, h, w), dys, cout, ks, pad, (cout, cin, ks, ks), terms=3)
         assert torch.equal(dw, dw2) and torch.equal(db, db2), name
@@ -421,24 +431,33 @@ def test_weight_gradient_with_many_slabs_against_fp64(case, monkeypatch):
         assert_close(db, dy.double().sum(dim=(0, 2, 3)), tol=2e-5, what=name + ": db")
         got[name] = dw
     assert not DEBUG_LIB or rel_err(got["shipped plan"], got["one-tap kernel"]) < 1e-5
+    # which kernel ran, by the library's own launch plan: filter rows for the 128 -> 128 layers, one tap per block for the two others
+    # and for every shape behind the switch
+    assert got["kernel of the shipped plan"].startswith("conv_wgrad_rows_bf16x3_kernel<%d, 8, 8, 0, 2>" % ks if (cin, cout) == (128, 128) else "conv_wgrad_bf16x3_kernel<4, 2>")
+    assert not DEBUG_LIB or got["kernel of the one-tap kernel"] == "conv_wgrad_bf16x3_kernel<4, 2>"
 
 
 def _bf16_round(t):
     return t.bfloat16().float()
 
 
+ROWS8, ROWS577 = "conv_wgrad_rows8_bf16x3_kernel<0, 1, 2>", "conv_wgrad_rows_bf16x3_kernel<5, 7, 7, 0, 1>"
 WGRAD_TERM_CASES = [
-    # N, Cin, H, W, Cout, ks, pad -- one per weight-gradient kernel instance the plan can pick
-    (8, 100, 44, 44, 100, 5, 0),     # conv_wgrad_rows8 (eight waves), one chunk per row
-    (2, 100, 30, 101, 100, 5, 2),    # conv_wgrad_rows8, two chunks per row (Wo = 101), padding
-    (2, 100, 40, 40, 441, 5, 0),     # conv_wgrad_rows8, four cout blocks
-    (2, 39, 40, 37, 100, 5, 0),      # conv_wgrad_rows<5,7,3>
-    (1, 256, 70, 35, 128, 3, 1),     # conv_wgrad_rows<3,8,8>, two cin blocks
-    (2, 64, 40, 37, 64, 3, 1),       # conv_wgrad_rows<3,4,4> / one-tap kernel (TM = 4)
-    (12, 128, 48, 40, 128, 1, 0),    # conv_wgrad_rows<1,8,8>
-    (16, 36, 64, 64, 64, 1, 0),      # one-tap kernel, TM = 4, many slabs
-    (2, 34, 11, 13, 100, 5, 0),      # one-tap kernel, TM = 7 (22 vectors per pixel over 4 threads: ragged)
-    (3, 128, 9, 10, 3, 1, 0),        # one-tap kernel, 3 couts
+    # N, Cin, H, W, Cout, ks, pad, the kernel of the three-term launch, of the one-term launch (asserted through
+    # wcmc_conv2d_wgrad_launch_plan_bf16x3 before the launches) -- one per weight-gradient kernel instance the plan can pick
+    (8, 100, 44, 44, 100, 5, 0, ROWS8, ROWS577),     # eight waves / seven, one chunk per row
+    # (N * Ho = 60 < 64 rows: NOT the filter-row kernel, as this row's comment said until the plan was asked; the next row is)
+    (2, 100, 30, 101, 100, 5, 2, "conv_wgrad_bf16x3_kernel<7, 2>", "conv_wgrad_bf16x3_kernel<7, 1>"),
+    (3, 100, 30, 101, 100, 5, 2, ROWS8, ROWS577),    # two chunks per row (Wo = 101), padding
+    (2, 100, 40, 40, 441, 5, 0, ROWS8, ROWS577),     # four cout blocks
+    (2, 39, 40, 37, 100, 5, 0, "conv_wgrad_rows_bf16x3_kernel<5, 7, 3, 0, 2>", "conv_wgrad_rows_bf16x3_kernel<5, 7, 3, 0, 1>"),
+    (1, 256, 70, 35, 128, 3, 1, "conv_wgrad_rows_bf16x3_kernel<3, 8, 8, 0, 2>", "conv_wgrad_rows_bf16x3_kernel<3, 8, 8, 0, 1>"),     # two cin blocks
+    (2, 64, 40, 37, 64, 3, 1, "conv_wgrad_rows_bf16x3_kernel<3, 4, 4, 0, 2>", "conv_wgrad_rows_bf16x3_kernel<3, 4, 4, 0, 1>"),
+    (12, 128, 48, 40, 128, 1, 0, "conv_wgrad_rows_bf16x3_kernel<1, 8, 8, 0, 2>", "conv_wgrad_rows_bf16x3_kernel<1, 8, 8, 0, 1>"),
+    # the one-tap kernel: TM = 4 with many slabs, TM = 7 (22 vectors per pixel over 4 threads: ragged), 3 couts
+    (16, 36, 64, 64, 64, 1, 0, "conv_wgrad_bf16x3_kernel<4, 2>", "conv_wgrad_bf16x3_kernel<4, 1>"),
+    (2, 34, 11, 13, 100, 5, 0, "conv_wgrad_bf16x3_kernel<7, 2>", "conv_wgrad_bf16x3_kernel<7, 1>"),
+    (3, 128, 9, 10, 3, 1, 0, "conv_wgrad_bf16x3_kernel<4, 2>", "conv_wgrad_bf16x3_kernel<4, 1>"),
 ]
 
 
@@ -450,7 +469,7 @@ def test_one_term_weight_gradient_is_the_three_term_one_on_bf16_operands(case, m
     both must sit on the fp64 value.  On general operands the one-term result is the exact gradient of the rounded operands:
     checked against fp64 on the rounded values at the same tolerance."""
     o = ops()
-    n, cin, h, w, cout, ks, pad = case
+    n, cin, h, w, cout, ks, pad, kernel3, kernel1 = case
     ho, wo = h + 2 * pad - ks + 1, w + 2 * pad - ks + 1
     x, dy = gen(n, cin, h, w, seed=190), gen(n, cout, ho, wo, seed=191)
     xb, dyb = _bf16_round(x), _bf16_round(dy)
@@ -460,6 +479,9 @@ def test_one_term_weight_gradient_is_the_three_term_one_on_bf16_operands(case, m
         monkeypatch.delenv("WCMC_WGRAD_ROWS", raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+        for terms, kernel in ((3, kernel3), (1, kernel1)):      # (WCMC_WGRAD_ROWS=0: the one-tap kernel, whatever the shape)
+            planned = o.wgrad_launch_plan(n, h, w, cin, cout, ks, pad, terms)[1]
+            assert planned.startswith("conv_wgrad_bf16x3_kernel<") if env else planned == kernel, (env, terms, planned)
         dw3, db3 = o.conv2d_wgrad_x_raw(xs, (n, cin, h, w), dys, cout, ks, pad, (cout, cin, ks, ks), terms=3)
         dw1, db1 = o.conv2d_wgrad_x_raw(xs, (n, cin, h, w), dys, cout, ks, pad, (cout, cin, ks, ks), terms=1)
         assert torch.equal(dw1, dw3) and torch.equal(db1, db3), env
@@ -473,7 +495,30 @@ def test_one_term_weight_gradient_is_the_three_term_one_on_bf16_operands(case, m
     assert rel_err(dw1, full) < 1.5e-2          # (2^-9 per operand, uncorrelated from pixel to pixel)
 
 
+def _fp32_view_strides(cout, ho, wo):
+    """(sn, sh, sw) of the fp32 NHWC view a launch with out_split=False writes (ops.nhwc_empty)."""
+    cp = (cout + 3) // 4 * 4
+    return (ho * wo * cp, wo * cp, cp)
+
+
+def _x_planes(kernel):
+    """Planes of x the named GEMM instance multiplies (its AP template argument): 2 = a three-term instance."""
+    args = [a.strip() for a in kernel[kernel.index("<") + 1:-1].split(",")]
+    return int(args[5]) if kernel.startswith("conv_halo64_") else int(args[-1]) if kernel.startswith("conv_halo_") else int(args[0]) if kernel.startswith("conv_halo3_") else 2
+
+
 TWO_TERM_FALLBACKS = ((2, 100, 30, 29, 39, 4, 5), (2, 120, 24, 24, 100, 4, 5), (2, 64, 20, 20, 32, 1, 3))
+H64X2, H3X2 = "conv_halo64_bf16x3_kernel<7, 3, 4, 0, 80, 1, 2, 0>", "conv_halo3_bf16x3_kernel<1, %d, 2, 0>"
+TWO_TERM_KERNELS = {      # the instance of the two-term launch with the fp32 output, by case (asserted through wcmc_conv2d_launch_plan_bf16x3)
+    (8, 100, 44, 44, 100, 0, 5): H64X2, (2, 100, 36, 36, 100, 4, 5): H64X2, (1, 441, 40, 37, 100, 4, 5): H64X2, (2, 232, 24, 24, 100, 4, 5): H64X2,
+    (2, 64, 40, 37, 64, 1, 3): H3X2 % 2, (1, 128, 37, 21, 128, 1, 3): H3X2 % 4, (2, 192, 24, 24, 64, 1, 3): "conv_halo_bf16x3_kernel<4, 8, 16, 0, 2, 1>",
+    (1, 384, 33, 18, 128, 1, 3): H3X2 % 4,
+    (1, 256, 20, 36, 192, 1, 3): H3X2 % 4,      # (12 cout tiles are three blocks of 64 couts of conv_halo3, not NT = 7 of conv_halo: the next case is)
+    (1, 256, 20, 36, 112, 1, 3): "conv_halo_bf16x3_kernel<7, 16, 16, 0, 3, 1>",
+    (1, 40, 20, 20, 64, 1, 3): "conv_halo_bf16x3_kernel<4, 8, 16, 0, 2, 1>", (8, 64, 128, 128, 64, 1, 3): H3X2 % 2,
+    (2, 32, 21, 23, 3, 4, 5): "conv_halo64_bf16x3_kernel<1, 3, 3, 0, 80, 1, 2, 0>", (1, 40, 19, 27, 8, 4, 5): "conv_halo64_bf16x3_kernel<1, 3, 3, 0, 80, 1, 2, 0>",
+    (2, 100, 25, 21, 16, 4, 5): "conv_halo64_bf16x3_kernel<1, 3, 3, 0, 80, 1, 2, 0>", (1, 100, 17, 33, 3, 4, 5): "conv_halo64_bf16x3_kernel<1, 3, 3, 0, 80, 1, 2, 0>",
+    (3, 32, 13, 40, 16, 4, 5): "conv_halo64_bf16x3_kernel<1, 3, 3, 0, 80, 1, 2, 0>"}
 
 
 @pytest.mark.parametrize("case", ((8, 100, 44, 44, 100, 0, 5), (2, 100, 36, 36, 100, 4, 5), (1, 441, 40, 37, 100, 4, 5), (2, 232, 24, 24, 100, 4, 5),
@@ -481,7 +526,7 @@ TWO_TERM_FALLBACKS = ((2, 100, 30, 29, 39, 4, 5), (2, 120, 24, 24, 100, 4, 5), (
                                   # slabs, conv_halo_bf16x3_kernel<4 | 7, .., AP = 1> elsewhere): one 64- / 128-channel slab, two of 96,
                                   # three of 128, 12 cout tiles (NT = 7), a 40-channel slab, ragged tiles, the benchmark's shape
                                   (2, 64, 40, 37, 64, 1, 3), (1, 128, 37, 21, 128, 1, 3), (2, 192, 24, 24, 64, 1, 3), (1, 384, 33, 18, 128, 1, 3),
-                                  (1, 256, 20, 36, 192, 1, 3), (1, 40, 20, 20, 64, 1, 3), (8, 64, 128, 128, 64, 1, 3),
+                                  (1, 256, 20, 36, 192, 1, 3), (1, 256, 20, 36, 112, 1, 3), (1, 40, 20, 20, 64, 1, 3), (8, 64, 128, 128, 64, 1, 3),
                                   # the ONE-cout-tile 5x5 instance (conv_halo64<1, 3, PT, 0, 80, 1>: x_plan_k grants it to every two-term 5x5
                                   # launch with at most 16 output rows, not only to the sliced first-layer gradient of KPCN): 3 / 8 / 16
                                   # rows, 32 / 40 / 100 channels (Kp % 32 = 0 and 8), odd sizes with partial tiles
@@ -508,6 +553,8 @@ def test_two_term_data_gradient_against_fp64(case):
     # the data-gradient GEMM: conv of x with the flipped, channel-swapped filter
     wf = wt.flip(2, 3).transpose(0, 1).contiguous()
     want = F.conv2d((x if fallback else xb).double(), wf.double(), padding=pad)
+    kernel = o.conv_launch_plan(n, h, w, cin, cout, ks, pad, 2, False, _fp32_view_strides(cout, ho, wo))[1]
+    assert _x_planes(kernel) == 2 if fallback else kernel == TWO_TERM_KERNELS[case], kernel      # (a fallback runs a three-term instance)
     y2 = o.conv2d_x_raw(xs, (n, cin, h, w), wp2, None, cout, ks, pad, "linear", out_split=False, terms=2)
     assert_close(y2, want, tol=2e-5, what="two-term dgrad (general x = its hi plane)")
     y2b = o.conv2d_x_raw(xbs, (n, cin, h, w), wp2, None, cout, ks, pad, "linear", out_split=False, terms=2)
@@ -525,6 +572,9 @@ def test_two_term_data_gradient_against_fp64(case):
 
 
 ONE_TERM_FALLBACKS = ((2, 100, 20, 21, 39, 0, 5), (2, 120, 20, 20, 100, 0, 5), (2, 64, 20, 20, 128, 1, 3))
+# pixel tiles per wave (PT) of the one-MFMA instance each case runs: 16-row tiles (4; 92 output rows: mixed with 12-row ones) or 12-row tiles (3)
+ONE_TERM_PT = {(8, 100, 96, 96, 441, 0, 5): 4, (1, 100, 40, 37, 441, 0, 5): 3, (2, 100, 36, 36, 100, 4, 5): 4, (1, 104, 30, 30, 112, 0, 5): 3,
+               (2, 72, 24, 27, 100, 0, 5): 3}
 
 
 @pytest.mark.parametrize("case", ((8, 100, 96, 96, 441, 0, 5), (1, 100, 40, 37, 441, 0, 5), (2, 100, 36, 36, 100, 4, 5), (1, 104, 30, 30, 112, 0, 5),
@@ -551,6 +601,14 @@ def test_one_term_output_layer_forward_is_exact_on_the_rounded_operands(case):
     wp1, wp1b, wp3b = o._pack_x(wd, 3), o._pack_x(wbd, 3), o._pack_x(wbd, 0)
     fallback = case in ONE_TERM_FALLBACKS
     run = lambda xs_, wp, t: o.conv2d_x_raw(xs_, (n, cin, h, w), wp, bd, cout, ks, pad, "linear", out_split=False, terms=t)
+    ho, wo = h + 2 * pad - ks + 1, w + 2 * pad - ks + 1
+    cls, kernel = o.conv_launch_plan(n, h, w, cin, cout, ks, pad, 1, False, _fp32_view_strides(cout, ho, wo))
+    # the one-MFMA instance and its class, or for a fallback the plan's own instance: three terms for the 5x5 cases, the two-term
+    # conv_halo3 instance for the 3x3 one (which is why its reference below is on the rounded x)
+    if fallback:
+        assert _x_planes(kernel) == (2 if ks == 5 else 1) and not cls.endswith("_x1"), (cls, kernel)
+    else:
+        assert (cls, kernel) == ("conv_halo64_pt%d_x1" % ONE_TERM_PT[case], "conv_halo64_bf16x3_kernel<7, 3, %d, 0, 80, 1, 1, 0>" % ONE_TERM_PT[case])
     y1 = run(xs, wp1, 1)
     if fallback:
         assert torch.equal(o._pack_x(wd, 0), wp1) or ks == 3      # (3x3: the hi-plane plan exists, the one-plane weight path does not)

@@ -49,6 +49,8 @@ SIGNATURES = {
     "wcmc_conv1x1_pair_bf16x3": (I, [P, I, I, I, I, P, P, I, I, F, P, P, P, I, F, P, P, P, I, I, F, P, L, L, L, P]),
     "wcmc_conv2d_igemm_colsum_elems": (Z, [I, I, I, I]),
     "wcmc_colsum_finish": (I, [P, I, I, I, I, P, P]),
+    "wcmc_conv2d_launch_plan_bf16x3": (I, [I, I, I, I, I, I, I, I, I, L, L, L, I, I, _c.c_char_p, _c.c_char_p, Z]),
+    "wcmc_conv2d_wgrad_launch_plan_bf16x3": (I, [I, I, I, I, I, I, I, I, _c.c_char_p, _c.c_char_p, Z]),
     "wcmc_conv2d_wgrad_bf16x3_workspace_bytes": (Z, [I, I, I, I, I, I]),
     "wcmc_conv2d_wgrad_reduce_multi": (I, [I, P, P, P, P, P, P, P, P, P, P, I, P]),
     "wcmc_conv2d_wgrad_bf16x3": (I, [P, I, I, I, I, P, I, I, I, P, P, P, Z, I, P, I, P]),

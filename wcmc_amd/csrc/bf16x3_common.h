@@ -155,20 +155,40 @@ __device__ __forceinline__ void pw_barrier() {
 
 int x_env_on(const char* name);           // conv_bf16x3.hip: switch is ON unless the variable starts with '0' (debug build only: ab_env)
 
-// ------------------------------------------------------------------ launch entries, one per family (its own unit defines it)
+// ------------------------------------------------------------------ launch plans and launch entries, one pair per family (its own unit defines it)
+// A plan function decides WHICH kernel instance a launch runs and its geometry: host arithmetic on the parameters (and, in the debug
+// build, the A/B switches, read per call) -- no HIP runtime call, so the launch-plan queries (wcmc_conv2d_launch_plan_bf16x3,
+// wcmc_conv2d_wgrad_launch_plan_bf16x3) ask the same code without a device.  A launcher runs the instance its plan names, or fails.
+// The fields that are template arguments are spelled as the kernel's: a kernel name is printed from them.
 // nt = x_pick_nt(p.Np / 16): cout tiles per block, one of {7, 4, 2, 1}
-int launch_xigemm(int nt, const XIgemmParams& p, hipStream_t stream);       // bf16x3_igemm.hip; halo plans go on to launch_xhalo
-int launch_xhalo(int nt, const XIgemmParams& p, hipStream_t stream);        // bf16x3_halo.hip; 5x5 plans of the 64-pixel kernel go on to launch_xhalo64
-int launch_xhalo64(int nt, const XIgemmParams& p, hipStream_t stream);      // bf16x3_halo64.hip
+struct XIgemmPlan { int nt, padded, dbuf; };                                    // conv_igemm_bf16x3_kernel<nt, padded, dbuf, 0>
+struct XHaloPlan { int nt, th, nb, ap, tilesY; size_t lds; };                   // conv_halo_bf16x3_kernel<nt, th, 16, 0, nb, ap>
+struct XHalo64Plan { int nt, nb, pt, pxst, ap, wp, f16;                         // conv_halo64_bf16x3_kernel<nt, nb, pt, 0, pxst, ap, wp, f16>
+                     int tilesX, tilesY, rows16, stripX, stripY; size_t lds; }; // ... and what the launch writes into its copy of the parameters
+struct XHalo3Plan { int ap, spt; };                                             // conv_halo3_bf16x3_kernel<ap, spt, 2, 0>
+struct XPwPlan { int ntw, u; };                                                 // conv_pw_bf16x3_kernel<ntw, u, split output, 0>
+struct XWRowsPlan { int ks, tm, nw, pl, rows8, xe; };                           // conv_wgrad_rows_bf16x3_kernel<ks, tm, nw, 0, pl> | rows8: conv_wgrad_rows8_bf16x3_kernel<0, xe, pl>
+// bf16x3_igemm.hip: plans without a halo (p.PXS == 0)
+XIgemmPlan x_plan_igemm(int nt, const XIgemmParams& p);
+int launch_xigemm(const XIgemmPlan& g, const XIgemmParams& p, hipStream_t stream);
+// bf16x3_halo.hip: halo plans (p.PXS != 0) but those of the 64-pixel 5x5 kernel (x_halo_is64); x_plan_halo fails where the tile does not fit in LDS
+bool x_halo_is64(const XIgemmParams& p);
+int x_plan_halo(int nt, const XIgemmParams& p, XHaloPlan* h);
+int launch_xhalo(const XHaloPlan& h, const XIgemmParams& p, hipStream_t stream);
+// bf16x3_halo64.hip
+XHalo64Plan x_plan_halo64(int nt, const XIgemmParams& p);
+int launch_xhalo64(const XHalo64Plan& h, const XIgemmParams& p, hipStream_t stream);
 // bf16x3_halo3.hip: the 3x3 plans of conv_halo3_bf16x3_kernel
 bool x_halo3_ok(const XIgemmParams& p);
-int launch_xhalo3(const XIgemmParams& p, hipStream_t stream);
+XHalo3Plan x_plan_halo3(const XIgemmParams& p);
+int launch_xhalo3(const XHalo3Plan& h, const XIgemmParams& p, hipStream_t stream);
 // bf16x3_pw.hip: x_plan_pw picks the pointwise instance (ntw waves, u 16-byte units per pixel) or says no; launch_xpw sets p.y_bytes / p.m_bytes
-bool x_plan_pw(const XIgemmParams& p, int* ntw, int* u);
-int launch_xpw(XIgemmParams& p, int ntw, int u, hipStream_t stream);
+bool x_plan_pw(const XIgemmParams& p, XPwPlan* w);
+int launch_xpw(XIgemmParams& p, const XPwPlan& w, hipStream_t stream);
 int launch_xpw_pair(int kind, const XIgemmParams& p, hipStream_t stream);      // kind = x_pair_kind(...): 1..3, the fused two-layer instances
 // bf16x3_wgrad.hip; planes: 2 = three MFMAs per product, 1 = the hi planes only
 int launch_xwgrad(int tm, int planes, const XWgradParams& p, hipStream_t stream);                            // tm = XWgradPlan::TM: 7 or 4
-int launch_xwgrad_rows(int ks, int tm, int nw, int planes, const XWRowsParams& p, hipStream_t stream);      // (tm, nw) = XWgradPlan::rTM, rNW
+XWRowsPlan x_plan_wgrad_rows(int ks, int tm, int nw, int planes);                                            // (tm, nw) = XWgradPlan::rTM, rNW
+int launch_xwgrad_rows(const XWRowsPlan& r, const XWRowsParams& p, hipStream_t stream);
 
 }  // namespace wcmc

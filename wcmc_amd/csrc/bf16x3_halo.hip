@@ -414,26 +414,20 @@ __global__ __launch_bounds__(TH * TW * 2, (TH * TW <= 128 ? 2 : 1)) void conv_ha
 
 using namespace wcmc;
 
-template <int NT, int NB, int AP = 2>
-static int launch_xhalo2(const XIgemmParams& p, size_t lds, hipStream_t stream) {
-  constexpr int TH = 16, TW = 16;
-  static LdsAttr attr;
-  if (set_max_lds(reinterpret_cast<const void*>(&conv_halo_bf16x3_kernel<NT, TH, TW, 0, NB, AP>), lds, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
-  const dim3 grid((unsigned)(p.N * p.tilesX * p.tilesY), (unsigned)((p.Np / 16 + NT - 1) / NT));
-  hipLaunchKernelGGL((conv_halo_bf16x3_kernel<NT, TH, TW, 0, NB, AP>), grid, dim3(512), lds, stream, p);
-  return check_launch("conv2d_igemm_bf16x3(halo)");
+static size_t xh_bstage_bytes(int nt) { return (size_t)(2 * nt * 16 * XROW + 64) * sizeof(u16); }      // one weight stage
+namespace wcmc {
+// halo plans of the 64-pixel 5x5 kernel (bf16x3_halo64.hip)
+bool x_halo_is64(const XIgemmParams& p) {
+  return (p.CS == 16 || p.ap == 1 ||
+          (p.CS == 32 && p.PXS == 160 && p.CSl == 32 && p.Kp >= 256 && x_env_on("WCMC_HALO64") && x_env_on("WCMC_HALO64_CS32"))) &&
+         p.ks == 5;
 }
-template <int NT>
-static int launch_xhalo(const XIgemmParams& p, hipStream_t stream) {
-  if ((p.CS == 16 || p.ap == 1 ||
-       (p.CS == 32 && p.PXS == 160 && p.CSl == 32 && p.Kp >= 256 && x_env_on("WCMC_HALO64") && x_env_on("WCMC_HALO64_CS32"))) &&
-      p.ks == 5)
-    return launch_xhalo64(NT, p, stream);
+int x_plan_halo(int nt, const XIgemmParams& p, XHaloPlan* h) {
   constexpr int TH = 16, TW = 16;
   const int HP = (TH + p.ks - 1) * (TW + p.ks - 1);
-  const size_t halo = (size_t)((HP * p.PXS + 127) & ~127), bstage = (size_t)(2 * NT * 16 * XROW + 64) * sizeof(u16);
-  const size_t lds_out = p.ys ? (size_t)256 * (2 * NT * 16 + 8) * sizeof(u16) + (size_t)32 * NT * 16 * sizeof(float)
-                              : (size_t)256 * (NT * 16 + 4) * sizeof(float);
+  const size_t halo = (size_t)((HP * p.PXS + 127) & ~127), bstage = xh_bstage_bytes(nt);
+  const size_t lds_out = p.ys ? (size_t)256 * (2 * nt * 16 + 8) * sizeof(u16) + (size_t)32 * nt * 16 * sizeof(float)
+                              : (size_t)256 * (nt * 16 + 4) * sizeof(float);
   // three weight stages (two stages of DMA latency cover) where LDS allows, else two
   const char* nbe = ab_env("WCMC_HALO_NB");
   const int nbmax = (nbe && nbe[0] == '2') ? 2 : 3;
@@ -441,7 +435,50 @@ static int launch_xhalo(const XIgemmParams& p, hipStream_t stream) {
   const size_t lds_main = halo + nb * bstage;
   const size_t lds = lds_main > lds_out ? lds_main : lds_out;
   WCMC_REQUIRE(lds <= 160 * 1024, WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: halo tile does not fit in LDS");
+  h->nt = nt;
+  h->ap = ((nt == 4 || nt == 7) && p.ap == 1) ? 1 : 2;      // (x_plan_k grants ap = 1 to this kernel for ks = 3 and nt = 4 or 7 only)
+  // ... and for any launch whose 16x16 tiling has fewer workgroups than the chip has CUs (the deepest U-Net level: 32 tiles
+  // x 4 cout blocks), where half-size tiles simply fill the machine (<= 4 cout tiles: one wave per weight row group pair)
+  const int64_t blocks16 = (int64_t)p.N * p.tilesX * p.tilesY * ((p.Np / 16 + nt - 1) / nt);
+  // ... and, measured (scripts/time_unet_layers.py), where the 16x16 tiling is two or more rounds (the 128^2 level: 512
+  // tiles): two 128-pixel workgroups per CU with their own stage barriers instead of one of 256 -- 46.8 -> 43.5 us
+  const bool underfilled = nt <= 4 && (blocks16 < 256 || blocks16 >= 512) && p.Ho >= 16;
+  if ((p.PXS == 160 && p.ks == 5) || underfilled) {
+    // WCMC_HALO_TH8_5X5 plan (32-channel slabs): 8x16-pixel tiles, four waves, TWO workgroups per CU -- their stage
+    // barriers are independent, so the non-MFMA phases of one hide behind the MFMAs of the other
+    constexpr int TH8 = 8;
+    const size_t halo8 = (size_t)(((TH8 + p.ks - 1) * (TW + p.ks - 1) * p.PXS + 127) & ~127);
+    const size_t out8 = p.ys ? (size_t)TH8 * TW * (2 * nt * 16 + 8) * sizeof(u16) + (size_t)32 * nt * 16 * sizeof(float)
+                             : (size_t)TH8 * TW * (nt * 16 + 4) * sizeof(float);
+    // (three weight stages, which still fit beside the second workgroup for <= 4 cout tiles, measured no faster on the
+    // U-Net's 3x3 layers, nor five in the 16x16 tiling: wall-clock stamps show 15 us in the stage loop of 64 -> 64 at
+    // 128^2 for 7 us of MFMAs, but the DMA is not what the stages wait for -- scripts/timeline_halo.py --unet)
+    const size_t main8 = halo8 + 2 * bstage;
+    h->th = TH8; h->nb = 2; h->tilesY = (p.Ho + TH8 - 1) / TH8; h->lds = main8 > out8 ? main8 : out8;
+  } else {
+    h->th = TH; h->nb = nb; h->tilesY = p.tilesY; h->lds = lds;
+  }
+  return 0;
+}
+}  // namespace wcmc
+
+template <int NT, int TH, int NB, int AP = 2>
+static int launch_xhalo2(const XHaloPlan& h, const XIgemmParams& p, hipStream_t stream) {
+  constexpr int TW = 16;
+  WCMC_REQUIRE(h.nt == NT && h.th == TH && h.nb == NB && h.ap == AP, WCMC_ERR_LAUNCH, "conv2d_igemm_bf16x3(halo): no instance for the plan");
+  static LdsAttr attr;
+  if (set_max_lds(reinterpret_cast<const void*>(&conv_halo_bf16x3_kernel<NT, TH, TW, 0, NB, AP>), h.lds, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
+  XIgemmParams q = p;
+  q.tilesY = h.tilesY;
+  const dim3 grid((unsigned)(q.N * q.tilesX * q.tilesY), (unsigned)((q.Np / 16 + NT - 1) / NT));
+  hipLaunchKernelGGL((conv_halo_bf16x3_kernel<NT, TH, TW, 0, NB, AP>), grid, dim3(TH * TW * 2), h.lds, stream, q);
+  return check_launch(TH == 16 ? "conv2d_igemm_bf16x3(halo)" : AP == 1 ? "conv2d_igemm_bf16x3(halo, 8x16, x hi plane)" : "conv2d_igemm_bf16x3(halo, 8x16)");
+}
+template <int NT>
+static int launch_xhalo(const XHaloPlan& h, const XIgemmParams& p, hipStream_t stream) {
 #ifdef WCMC_DEBUG_BUILD
+  constexpr int TW = 16;
+  const size_t bstage = xh_bstage_bytes(NT);
   if (NT == 7 && p.PXS == 160 && p.ks == 5) {
     int ab;                             // (read per call: scripts interleave the modes inside one process)
     { const char* e = ab_env("WCMC_DEBUG_ABLATE"); ab = e ? atoi(e) : 0; }
@@ -476,8 +513,6 @@ static int launch_xhalo(const XIgemmParams& p, hipStream_t stream) {
       return check_launch("conv2d_igemm_bf16x3(halo 8x16, stamps)");
     }
   }
-#endif
-#ifdef WCMC_DEBUG_BUILD
   if (NT == 4 && p.ks == 3) {        // wall-clock stamps of the U-Net 3x3 launches, 8x16 tiling (scripts/timeline_halo.py --unet)
     const char* e = ab_env("WCMC_DEBUG_ABLATE");
     if (e && atoi(e) == 64) {
@@ -495,52 +530,18 @@ static int launch_xhalo(const XIgemmParams& p, hipStream_t stream) {
     }
   }
 #endif
-  // ... and for any launch whose 16x16 tiling has fewer workgroups than the chip has CUs (the deepest U-Net level: 32 tiles
-  // x 4 cout blocks), where half-size tiles simply fill the machine (<= 4 cout tiles: one wave per weight row group pair)
-  const int64_t blocks16 = (int64_t)p.N * p.tilesX * p.tilesY * ((p.Np / 16 + NT - 1) / NT);
-  // ... and, measured (scripts/time_unet_layers.py), where the 16x16 tiling is two or more rounds (the 128^2 level: 512
-  // tiles): two 128-pixel workgroups per CU with their own stage barriers instead of one of 256 -- 46.8 -> 43.5 us
-  const bool underfilled = NT <= 4 && (blocks16 < 256 || blocks16 >= 512) && p.Ho >= 16;
-  if ((p.PXS == 160 && p.ks == 5) || underfilled) {
-    // WCMC_HALO_TH8_5X5 plan (32-channel slabs): 8x16-pixel tiles, four waves, TWO workgroups per CU -- their stage
-    // barriers are independent, so the non-MFMA phases of one hide behind the MFMAs of the other
-    constexpr int TH8 = 8;
-    XIgemmParams q = p;
-    q.tilesY = (p.Ho + TH8 - 1) / TH8;
-    const size_t halo8 = (size_t)(((TH8 + p.ks - 1) * (TW + p.ks - 1) * p.PXS + 127) & ~127);
-    const size_t out8 = p.ys ? (size_t)TH8 * TW * (2 * NT * 16 + 8) * sizeof(u16) + (size_t)32 * NT * 16 * sizeof(float)
-                             : (size_t)TH8 * TW * (NT * 16 + 4) * sizeof(float);
-    // (three weight stages, which still fit beside the second workgroup for <= 4 cout tiles, measured no faster on the
-    // U-Net's 3x3 layers, nor five in the 16x16 tiling: wall-clock stamps show 15 us in the stage loop of 64 -> 64 at
-    // 128^2 for 7 us of MFMAs, but the DMA is not what the stages wait for -- scripts/timeline_halo.py --unet)
-    const size_t main8 = halo8 + 2 * bstage;
-    const size_t lds8 = main8 > out8 ? main8 : out8;
-    const dim3 grid((unsigned)(q.N * q.tilesX * q.tilesY), (unsigned)((q.Np / 16 + NT - 1) / NT));
-    if constexpr (NT == 4 || NT == 7) {
-      if (p.ap == 1) {                           // (x_plan_k grants ap = 1 to this kernel for ks = 3 and NT = 4 or 7 only)
-        static LdsAttr attr81;
-        if (set_max_lds(reinterpret_cast<const void*>(&conv_halo_bf16x3_kernel<NT, TH8, TW, 0, 2, 1>), lds8, attr81) != hipSuccess) return WCMC_ERR_LAUNCH;
-        hipLaunchKernelGGL((conv_halo_bf16x3_kernel<NT, TH8, TW, 0, 2, 1>), grid, dim3(TH8 * TW * 2), lds8, stream, q);
-        return check_launch("conv2d_igemm_bf16x3(halo, 8x16, x hi plane)");
-      }
-    }
-    static LdsAttr attr8;
-    if (set_max_lds(reinterpret_cast<const void*>(&conv_halo_bf16x3_kernel<NT, TH8, TW, 0, 2>), lds8, attr8) != hipSuccess) return WCMC_ERR_LAUNCH;
-    hipLaunchKernelGGL((conv_halo_bf16x3_kernel<NT, TH8, TW, 0, 2>), grid, dim3(TH8 * TW * 2), lds8, stream, q);
-    return check_launch("conv2d_igemm_bf16x3(halo, 8x16)");
-  }
   if constexpr (NT == 4 || NT == 7) {
-    if (p.ap == 1) return nb == 3 ? launch_xhalo2<NT, 3, 1>(p, lds, stream) : launch_xhalo2<NT, 2, 1>(p, lds, stream);
+    if (h.ap == 1) return h.th == 8 ? launch_xhalo2<NT, 8, 2, 1>(h, p, stream) : h.nb == 3 ? launch_xhalo2<NT, 16, 3, 1>(h, p, stream) : launch_xhalo2<NT, 16, 2, 1>(h, p, stream);
   }
-  return nb == 3 ? launch_xhalo2<NT, 3>(p, lds, stream) : launch_xhalo2<NT, 2>(p, lds, stream);
+  return h.th == 8 ? launch_xhalo2<NT, 8, 2>(h, p, stream) : h.nb == 3 ? launch_xhalo2<NT, 16, 3>(h, p, stream) : launch_xhalo2<NT, 16, 2>(h, p, stream);
 }
 namespace wcmc {
-int launch_xhalo(int nt, const XIgemmParams& p, hipStream_t stream) {      // nt: x_pick_nt's choice
-  switch (nt) {
-    case 7: return ::launch_xhalo<7>(p, stream);
-    case 4: return ::launch_xhalo<4>(p, stream);
-    case 2: return ::launch_xhalo<2>(p, stream);
-    default: return ::launch_xhalo<1>(p, stream);
+int launch_xhalo(const XHaloPlan& h, const XIgemmParams& p, hipStream_t stream) {
+  switch (h.nt) {
+    case 7: return ::launch_xhalo<7>(h, p, stream);
+    case 4: return ::launch_xhalo<4>(h, p, stream);
+    case 2: return ::launch_xhalo<2>(h, p, stream);
+    default: return ::launch_xhalo<1>(h, p, stream);
   }
 }
 }  // namespace wcmc

@@ -376,8 +376,13 @@ bool x_halo3_ok(const XIgemmParams& p) {
   if (p.ap == 2) return p.CS == 64 && p.CSl == 64 && p.SPS == 18 && p.SPSl == 18;
   return (p.CS == 64 && p.nslabs == 1 && p.SPSl == 18) || (p.CS == 128 && p.CSl == 128 && p.SPS == 36 && p.SPSl == 36);
 }
+// two MFMAs per product (hi plane of x only): 128-channel slabs take four stages per tap, 64-channel ones two, as every two-plane slab
+XHalo3Plan x_plan_halo3(const XIgemmParams& p) {
+  return XHalo3Plan{p.ap == 2 ? 2 : 1, (p.ap != 2 && p.CS == 128) ? 4 : 2};
+}
 template <int AP, int SPT>
-static int launch_xhalo3b(const XIgemmParams& q, hipStream_t stream) {
+static int launch_xhalo3b(const XHalo3Plan& h, const XIgemmParams& q, hipStream_t stream) {
+  WCMC_REQUIRE(h.ap == AP && h.spt == SPT, WCMC_ERR_LAUNCH, "conv2d_igemm_bf16x3(halo 3x3, K groups): no instance for the plan");
   constexpr int KG = 2;
   const size_t lds = (size_t)180 * 256 + (size_t)2 * KG * (2 * 64 * XROW + 64) * sizeof(u16);      // 79,360 B: two workgroups per CU
   static LdsAttr attr;
@@ -410,12 +415,12 @@ static int launch_xhalo3b(const XIgemmParams& q, hipStream_t stream) {
   hipLaunchKernelGGL((conv_halo3_bf16x3_kernel<AP, SPT, KG>), grid, dim3(256 * KG), lds, stream, q);
   return check_launch("conv2d_igemm_bf16x3(halo 3x3, K groups)");
 }
-int launch_xhalo3(const XIgemmParams& p, hipStream_t stream) {
+int launch_xhalo3(const XHalo3Plan& h, const XIgemmParams& p, hipStream_t stream) {
   XIgemmParams q = p;
   q.tilesY = (p.Ho + 7) / 8;
   q.PXS = 256;
-  if (p.ap == 2) return launch_xhalo3b<2, 2>(q, stream);
-  return p.CS == 128 ? launch_xhalo3b<1, 4>(q, stream) : launch_xhalo3b<1, 2>(q, stream);
+  if (h.ap == 2) return launch_xhalo3b<2, 2>(h, q, stream);
+  return h.spt == 4 ? launch_xhalo3b<1, 4>(h, q, stream) : launch_xhalo3b<1, 2>(h, q, stream);
 }
 
 }  // namespace wcmc

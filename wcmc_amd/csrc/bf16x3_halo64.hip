@@ -487,37 +487,16 @@ __global__ __launch_bounds__(256, 2) void conv_halo64_bf16x3_kernel(XIgemmParams
   }
 }
 
-template <int NT, int NB, int PT, int PXST, int AP = 2, int WP = 2, int F16 = 0>
-static int launch_xhalo64c(const XIgemmParams& p, size_t lds, hipStream_t stream) {
-  static LdsAttr attr;
-  if (set_max_lds(reinterpret_cast<const void*>(&conv_halo64_bf16x3_kernel<NT, NB, PT, 0, PXST, AP, WP, F16>), lds, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
-  const dim3 grid((unsigned)(p.N * (p.tilesX * p.tilesY + (PT == 4 ? p.stripX * p.stripY : 0))), (unsigned)((p.Np / 16 + NT - 1) / NT));
-  hipLaunchKernelGGL((conv_halo64_bf16x3_kernel<NT, NB, PT, 0, PXST, AP, WP, F16>), grid, dim3(256), lds, stream, p);
-  return check_launch("conv2d_igemm_bf16x3(halo, 64 pixels per wave)");
-}
-template <int NT, int NB, int PT>
-static int launch_xhalo64b(const XIgemmParams& p, size_t lds, hipStream_t stream) {
-  // the halo pixel stride as a template constant for the two shipped values (NB = 3: 16-channel slabs, 80 B; NB = 2 with
-  // 12x16 tiles: 32-channel slabs, 160 B); anything else (WCMC_HALO64_PXS, WCMC_HALO_NB experiments) reads it from the params
-  if constexpr (NT == 7 && NB == 3) {
-    if (p.ap == 1 && p.wplanes == 1 && p.f16) return launch_xhalo64c<NT, NB, PT, 80, 1, 1, 1>(p, lds, stream);      // one fp16 MFMA per product ("bf16x321h" output layers)
-    if (p.ap == 1 && p.wplanes == 1) return launch_xhalo64c<NT, NB, PT, 80, 1, 1>(p, lds, stream);      // one MFMA per product ("bf16x321o" output layers)
-  }
-  if constexpr ((NT == 7 || NT == 1) && NB == 3) {
-    if (p.ap == 1) return launch_xhalo64c<NT, NB, PT, 80, 1>(p, lds, stream);          // (x_plan_k grants ap = 1 with PXS = 80, ks = 5 only)
-  }
-  if (p.ks == 5 && p.PXS == 80 && NB == 3) return launch_xhalo64c<NT, NB, PT, NB == 3 ? 80 : 0>(p, lds, stream);
-  if (p.ks == 5 && p.PXS == 160 && NB == 2 && PT == 3) return launch_xhalo64c<NT, NB, PT, (NB == 2 && PT == 3) ? 160 : 0>(p, lds, stream);
-  return launch_xhalo64c<NT, NB, PT, 0>(p, lds, stream);
-}
-template <int NT>
-static int launch_xhalo64(const XIgemmParams& p0, hipStream_t stream) {
-  XIgemmParams p = p0;
-  p.SPS |= 0x100;     // alternate the priority of a CU's two workgroups stage by stage (measured neutral on the launch time, kept: it evens the two workgroups' finish times; its A/B switch is gone)
+static size_t xh64_halo_bytes(int th, const XIgemmParams& p) { return (size_t)(((th + p.ks - 1) * (16 + p.ks - 1) * p.PXS + 127) & ~127); }
+static size_t xh64_bstage_bytes(int nt) { return (size_t)(2 * nt * 16 * XROW + 64) * sizeof(u16); }      // one weight stage
+
+XHalo64Plan x_plan_halo64(int nt, const XIgemmParams& p) {
+  XHalo64Plan h;
+  h.nt = nt;
   // Tile height 16 (four pixel tiles per wave) or 12 (three): 512 workgroups are resident (two per CU), a launch takes
   // ceil(workgroups / 512) rounds of a time proportional to the tile height.  The KPCN layers of 100..108 output rows
   // are 392 tiles of 16x16 (one round, a quarter of the slots empty) but 504 of 12x16 (one round of 3/4 the length).
-  const int gy = (p.Np / 16 + NT - 1) / NT;
+  const int gy = (p.Np / 16 + nt - 1) / nt;
   auto rounds = [&](int th) { return ((int64_t)p.N * p.tilesX * ((p.Ho + th - 1) / th) * gy + 511) / 512 * th; };
   bool pt3 = p.PXS == 160 || (x_env_on("WCMC_HALO64_PT3") && rounds(12) < rounds(16));     // (32-channel slabs: 12x16 only)
   // 16 does not divide Ho (KPCN: 124, 120, 116, 108, 104, 100, 92 rows): a tile rows of 16 followed by b of 12 cover it EXACTLY -- the
@@ -529,22 +508,74 @@ static int launch_xhalo64(const XIgemmParams& p0, hipStream_t stream) {
   // the rule above stands (96 rows: 288 workgroups of 16 rows are slower than 384 of 12, in the step too).
   // Debug build, WCMC_HALO64_MIX: 0 = pure tilings, 1 = mix only where 12 does not divide Ho either; WCMC_HALO64_NOMIX=<Ho>: one
   // height keeps its pure tiling (the per-height A/B).
-  p.rows16 = 1 << 20; p.stripX = p.stripY = 0;
+  h.rows16 = 1 << 20; h.stripX = h.stripY = 0; h.tilesX = p.tilesX;
   const char* mixe = ab_env("WCMC_HALO64_MIX");
   const bool mix12 = !(mixe && mixe[0] == '1');
   const char* nomix = ab_env("WCMC_HALO64_NOMIX");
   if (p.PXS != 160 && p.Ho % 16 != 0 && (p.Ho % 12 != 0 || mix12) && x_env_on("WCMC_HALO64_MIX") && !(nomix && atoi(nomix) == p.Ho)) {
     for (int b = 1; 12 * b < p.Ho; ++b)
-      if ((p.Ho - 12 * b) % 16 == 0) { p.rows16 = (p.Ho - 12 * b) / 16; pt3 = false; break; }
+      if ((p.Ho - 12 * b) % 16 == 0) { h.rows16 = (p.Ho - 12 * b) / 16; pt3 = false; break; }
   }
-  const bool mixed = p.rows16 != (1 << 20);
+  const bool mixed = h.rows16 != (1 << 20);
   const int th = pt3 ? 12 : 16;
-  p.tilesY = mixed ? p.rows16 + (p.Ho - 16 * p.rows16) / 12 : (p.Ho + th - 1) / th;
-  const int HP = (th + p.ks - 1) * (16 + p.ks - 1);
-  const size_t halo = (size_t)((HP * p.PXS + 127) & ~127), bstage = (size_t)(2 * NT * 16 * XROW + 64) * sizeof(u16);
-  const size_t out = p.ys ? (size_t)128 * (2 * NT * 16 + 8) * sizeof(u16) : (size_t)128 * (NT * 16 + 4) * sizeof(float);
+  h.tilesY = mixed ? h.rows16 + (p.Ho - 16 * h.rows16) / 12 : (p.Ho + th - 1) / th;
+  const size_t halo = xh64_halo_bytes(th, p), bstage = xh64_bstage_bytes(nt);
+  const size_t out = p.ys ? (size_t)128 * (2 * nt * 16 + 8) * sizeof(u16) : (size_t)128 * (nt * 16 + 4) * sizeof(float);
+  // three weight stages where two workgroups still fit a CU (80 KB each), else two
+  const char* nbe = ab_env("WCMC_HALO_NB");
+  h.nb = (p.ap == 1 || (!(nbe && nbe[0] == '2') && halo + 3 * bstage <= 80 * 1024)) ? 3 : 2;
+  h.pt = pt3 ? 3 : 4;
+  // The width likewise: where 16 does not divide Wo, a tile columns of 16 + b columns of 12 cover it exactly; the b columns are a
+  // strip of workgroups that hold their halo transposed (see the kernel: 16 image rows x 12 image columns each, 16-row tile rows) --
+  // the 16-row instance only.  (WCMC_HALO64_STRIP=0, debug build: 16-wide tiles throughout.)
+  if (!pt3 && p.ks == 5 && p.Wo % 16 != 0 && p.Wo % 4 == 0 && x_env_on("WCMC_HALO64_STRIP")) {
+    for (int b = 1; b <= 3; ++b)
+      if (12 * b < p.Wo && (p.Wo - 12 * b) % 16 == 0) { h.stripX = b; h.tilesX = (p.Wo - 12 * b) / 16; h.stripY = (p.Ho + 15) / 16; break; }
+  }
+  const size_t main_ = halo + h.nb * bstage;
+  h.lds = main_ > out ? main_ : out;
+  // which instance: the hi-plane ones exist for three weight stages and seven cout tiles (one MFMA per product: wp = 1, fp16 operands:
+  // f16) or seven / one (two MFMAs: ap = 1; x_plan_k grants ap = 1 with PXS = 80, ks = 5 only); the halo pixel stride is a template
+  // constant for the two shipped values (nb = 3: 16-channel slabs, 80 B; nb = 2 with 12x16 tiles: 32-channel slabs, 160 B), anything
+  // else (WCMC_HALO_NB experiments) reads it from the params (pxst = 0)
+  const bool hi = h.nb == 3 && p.ap == 1;
+  h.wp = (hi && nt == 7 && p.wplanes == 1) ? 1 : 2;      // "bf16x321o" output layers
+  h.f16 = (h.wp == 1 && p.f16) ? 1 : 0;                  // "bf16x321h" output layers
+  h.ap = (hi && (nt == 7 || nt == 1)) ? 1 : 2;
+  h.pxst = h.ap == 1 ? 80 : (p.ks == 5 && p.PXS == 80 && h.nb == 3) ? 80 : (p.ks == 5 && p.PXS == 160 && h.nb == 2 && pt3) ? 160 : 0;
+  return h;
+}
+
+template <int NT, int NB, int PT, int PXST, int AP = 2, int WP = 2, int F16 = 0>
+static int launch_xhalo64c(const XHalo64Plan& h, const XIgemmParams& p, hipStream_t stream) {
+  WCMC_REQUIRE(h.nt == NT && h.nb == NB && h.pt == PT && h.pxst == PXST && h.ap == AP && h.wp == WP && h.f16 == F16, WCMC_ERR_LAUNCH,
+               "conv2d_igemm_bf16x3(halo, 64 pixels per wave): no instance for the plan");
+  static LdsAttr attr;
+  if (set_max_lds(reinterpret_cast<const void*>(&conv_halo64_bf16x3_kernel<NT, NB, PT, 0, PXST, AP, WP, F16>), h.lds, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
+  const dim3 grid((unsigned)(p.N * (p.tilesX * p.tilesY + (PT == 4 ? p.stripX * p.stripY : 0))), (unsigned)((p.Np / 16 + NT - 1) / NT));
+  hipLaunchKernelGGL((conv_halo64_bf16x3_kernel<NT, NB, PT, 0, PXST, AP, WP, F16>), grid, dim3(256), h.lds, stream, p);
+  return check_launch("conv2d_igemm_bf16x3(halo, 64 pixels per wave)");
+}
+template <int NT, int NB, int PT>
+static int launch_xhalo64b(const XHalo64Plan& h, const XIgemmParams& p, hipStream_t stream) {
+  if constexpr (NT == 7 && NB == 3) {
+    if (h.f16) return launch_xhalo64c<NT, NB, PT, 80, 1, 1, 1>(h, p, stream);
+    if (h.wp == 1) return launch_xhalo64c<NT, NB, PT, 80, 1, 1>(h, p, stream);
+  }
+  if constexpr ((NT == 7 || NT == 1) && NB == 3) {
+    if (h.ap == 1) return launch_xhalo64c<NT, NB, PT, 80, 1>(h, p, stream);
+  }
+  if (h.pxst == 80) return launch_xhalo64c<NT, NB, PT, NB == 3 ? 80 : 0>(h, p, stream);
+  if (h.pxst == 160) return launch_xhalo64c<NT, NB, PT, (NB == 2 && PT == 3) ? 160 : 0>(h, p, stream);
+  return launch_xhalo64c<NT, NB, PT, 0>(h, p, stream);
+}
+template <int NT>
+static int launch_xhalo64(const XHalo64Plan& h, const XIgemmParams& p0, hipStream_t stream) {
+  XIgemmParams p = p0;
+  p.SPS |= 0x100;     // alternate the priority of a CU's two workgroups stage by stage (measured neutral on the launch time, kept: it evens the two workgroups' finish times; its A/B switch is gone)
+  p.rows16 = h.rows16; p.tilesY = h.tilesY; p.stripX = p.stripY = 0;
 #ifdef WCMC_DEBUG_BUILD
-  if (NT == 7 && !pt3 && p.PXS == 80 && p.ks == 5) {
+  if (NT == 7 && h.pt == 4 && p.PXS == 80 && p.ks == 5) {
     const char* e = ab_env("WCMC_DEBUG_ABLATE");
     const int ab = e ? atoi(e) : 0;
     if (ab) {
@@ -555,32 +586,21 @@ static int launch_xhalo64(const XIgemmParams& p0, hipStream_t stream) {
                  : &conv_halo64_bf16x3_kernel<7, 3, 4, 64, 80>;
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
       const dim3 grid((unsigned)(p.N * p.tilesX * p.tilesY), (unsigned)((p.Np / 16 + NT - 1) / NT));
-      hipLaunchKernelGGL(kfn, grid, dim3(256), halo + 3 * bstage, stream, p);
+      hipLaunchKernelGGL(kfn, grid, dim3(256), xh64_halo_bytes(16, p) + 3 * xh64_bstage_bytes(NT), stream, p);
       return check_launch("conv2d_igemm_bf16x3(halo64, debug)");
     }
   }
 #endif
-  // three weight stages where two workgroups still fit a CU (80 KB each), else two
-  const char* nbe = ab_env("WCMC_HALO_NB");
-  const int nb = (p.ap == 1 || (!(nbe && nbe[0] == '2') && halo + 3 * bstage <= 80 * 1024)) ? 3 : 2;
-  // The width likewise: where 16 does not divide Wo, a tile columns of 16 + b columns of 12 cover it exactly; the b columns are a
-  // strip of workgroups that hold their halo transposed (see the kernel: 16 image rows x 12 image columns each, 16-row tile rows) --
-  // the 16-row instance only.  (WCMC_HALO64_STRIP=0, debug build: 16-wide tiles throughout.)
-  if (!pt3 && p.ks == 5 && p.Wo % 16 != 0 && p.Wo % 4 == 0 && x_env_on("WCMC_HALO64_STRIP")) {
-    for (int b = 1; b <= 3; ++b)
-      if (12 * b < p.Wo && (p.Wo - 12 * b) % 16 == 0) { p.stripX = b; p.tilesX = (p.Wo - 12 * b) / 16; p.stripY = (p.Ho + 15) / 16; break; }
-  }
-  const size_t main_ = halo + nb * bstage;
-  const size_t lds = main_ > out ? main_ : out;
-  if (pt3) return nb == 3 ? launch_xhalo64b<NT, 3, 3>(p, lds, stream) : launch_xhalo64b<NT, 2, 3>(p, lds, stream);
-  return nb == 3 ? launch_xhalo64b<NT, 3, 4>(p, lds, stream) : launch_xhalo64b<NT, 2, 4>(p, lds, stream);
+  p.tilesX = h.tilesX; p.stripX = h.stripX; p.stripY = h.stripY;
+  if (h.pt == 3) return h.nb == 3 ? launch_xhalo64b<NT, 3, 3>(h, p, stream) : launch_xhalo64b<NT, 2, 3>(h, p, stream);
+  return h.nb == 3 ? launch_xhalo64b<NT, 3, 4>(h, p, stream) : launch_xhalo64b<NT, 2, 4>(h, p, stream);
 }
-int launch_xhalo64(int nt, const XIgemmParams& p, hipStream_t stream) {      // nt: x_pick_nt's choice
-  switch (nt) {
-    case 7: return launch_xhalo64<7>(p, stream);
-    case 4: return launch_xhalo64<4>(p, stream);
-    case 2: return launch_xhalo64<2>(p, stream);
-    default: return launch_xhalo64<1>(p, stream);
+int launch_xhalo64(const XHalo64Plan& h, const XIgemmParams& p, hipStream_t stream) {
+  switch (h.nt) {
+    case 7: return launch_xhalo64<7>(h, p, stream);
+    case 4: return launch_xhalo64<4>(h, p, stream);
+    case 2: return launch_xhalo64<2>(h, p, stream);
+    default: return launch_xhalo64<1>(h, p, stream);
   }
 }
 

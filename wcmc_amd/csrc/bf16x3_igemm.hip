@@ -353,7 +353,6 @@ __global__ __launch_bounds__(256, DBUF ? 2 : 3) void conv_igemm_bf16x3_kernel(XI
   }
 }
 
-static int g_xigemm_dbuf = -1;      // WCMC_IGEMM_DBUF=0/1 (A/B switch); default: double buffer
 template <int NT, bool PADDED, bool DBUF>
 static int launch_xigemm3(const XIgemmParams& p, hipStream_t stream) {
   const size_t lds_stage = (size_t)(DBUF ? 2 : 1) * (2 * XBM * XROW + 64 + 2 * NT * 16 * XROW + 64) * sizeof(u16);
@@ -377,7 +376,7 @@ static int launch_xigemm_dbg(const XIgemmParams& p, hipStream_t stream) {
 }
 #endif
 template <int NT, bool PADDED>
-static int launch_xigemm2(const XIgemmParams& p, hipStream_t stream) {
+static int launch_xigemm2(const XIgemmPlan& g, const XIgemmParams& p, hipStream_t stream) {
 #ifdef WCMC_DEBUG_BUILD
   if (NT == 7 && !PADDED) {       // WCMC_DEBUG_ABLATE=<mask>: timing-only ablation builds of the 5x5 forward GEMM
     static int ab = -1;
@@ -398,21 +397,22 @@ static int launch_xigemm2(const XIgemmParams& p, hipStream_t stream) {
     }
   }
 #endif
-  g_xigemm_dbuf = x_env_on("WCMC_IGEMM_DBUF");
-  return g_xigemm_dbuf ? launch_xigemm3<NT, PADDED, true>(p, stream) : launch_xigemm3<NT, PADDED, false>(p, stream);
+  return g.dbuf ? launch_xigemm3<NT, PADDED, true>(p, stream) : launch_xigemm3<NT, PADDED, false>(p, stream);
 }
 
 template <int NT>
-static int launch_xigemm(const XIgemmParams& p, hipStream_t stream) {
-  if (p.PXS) return launch_xhalo(NT, p, stream);
-  return p.pad > 0 ? launch_xigemm2<NT, true>(p, stream) : launch_xigemm2<NT, false>(p, stream);
+static int launch_xigemm(const XIgemmPlan& g, const XIgemmParams& p, hipStream_t stream) {
+  return g.padded ? launch_xigemm2<NT, true>(g, p, stream) : launch_xigemm2<NT, false>(g, p, stream);
 }
-int launch_xigemm(int nt, const XIgemmParams& p, hipStream_t stream) {      // nt: x_pick_nt's choice
-  switch (nt) {
-    case 7: return launch_xigemm<7>(p, stream);
-    case 4: return launch_xigemm<4>(p, stream);
-    case 2: return launch_xigemm<2>(p, stream);
-    default: return launch_xigemm<1>(p, stream);
+XIgemmPlan x_plan_igemm(int nt, const XIgemmParams& p) {
+  return XIgemmPlan{nt, p.pad > 0 ? 1 : 0, x_env_on("WCMC_IGEMM_DBUF")};      // WCMC_IGEMM_DBUF=0 (debug build): A/B switch to the single buffer
+}
+int launch_xigemm(const XIgemmPlan& g, const XIgemmParams& p, hipStream_t stream) {
+  switch (g.nt) {
+    case 7: return launch_xigemm<7>(g, p, stream);
+    case 4: return launch_xigemm<4>(g, p, stream);
+    case 2: return launch_xigemm<2>(g, p, stream);
+    default: return launch_xigemm<1>(g, p, stream);
   }
 }
 

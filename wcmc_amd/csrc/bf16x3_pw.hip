@@ -354,15 +354,15 @@ static int launch_xpw2(const XIgemmParams& p, hipStream_t stream) {
 }
 
 // 1x1, no padding, the channel counts of the PathNet chains; anything else stays on the tiled kernel
-bool x_plan_pw(const XIgemmParams& p, int* ntw, int* u) {
+bool x_plan_pw(const XIgemmParams& p, XPwPlan* w) {
   if (p.ks != 1 || p.pad != 0 || p.gate || p.PXS) return false;
   const char* e = ab_env("WCMC_IGEMM_PW");      // read per call: the parity tests switch kernels inside one process
   if (e && e[0] == '0') return false;
   const int U = p.Cpi / 4;
-  if (p.Np == 64 && (U == 16 || U == 10)) *ntw = 4;
-  else if (p.Np == 128 && (U == 32 || U == 2)) *ntw = 8;
+  if (p.Np == 64 && (U == 16 || U == 10)) w->ntw = 4;
+  else if (p.Np == 128 && (U == 32 || U == 2)) w->ntw = 8;
   else return false;
-  *u = U;
+  w->u = U;
   if (p.Cout != p.Np || p.Kt != (U > 16 ? 128 : U > 8 ? 64 : 32)) return false;
   if (p.M * 4 * p.Np >= 0x7ff00000LL) return false;
   if (p.yf) {
@@ -371,7 +371,8 @@ bool x_plan_pw(const XIgemmParams& p, int* ntw, int* u) {
   }
   return true;
 }
-int launch_xpw(XIgemmParams& p, int ntw, int u, hipStream_t st) {
+int launch_xpw(XIgemmParams& p, const XPwPlan& w, hipStream_t st) {
+  const int ntw = w.ntw, u = w.u;
   if (p.ys) {
     p.y_bytes = (unsigned)(p.M * 4 * p.Np);
     p.m_bytes = (unsigned)(p.M * (p.Np / 8));

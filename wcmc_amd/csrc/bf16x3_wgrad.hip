@@ -923,15 +923,10 @@ static constexpr size_t xwr_lds_bytes() {
 }
 
 template <int KS, int TM, int NW, int PL = 2>
-static int launch_xwgrad_rows(const XWRowsParams& q, hipStream_t st) {
+static int launch_xwgrad_rows(const XWRowsPlan& r, const XWRowsParams& q, hipStream_t st) {
   constexpr size_t lds = xwr_lds_bytes<KS, TM, NW, PL>();
   const dim3 grid((unsigned)(((q.S * q.coBlocks * q.ciBlocks + 7) / 8) * 8 * KS));
-  // The eight-wave kernel for the two-plane (three-term) launches, the seven-wave one for the one-plane launches of the default
-  // mode: there the seven waves are faster alone (0.311 against 0.295 of the bf16 peak in the eager profile) and beside the other
-  // half of the step (+0.9 % per step, round 4).  WCMC_WGRAD_ROWS8=1 / 0: eight / seven waves for both.
-  const char* r8e = ab_env("WCMC_WGRAD_ROWS8");
-  const bool rows8 = r8e ? r8e[0] != '0' : PL == 2;
-  if (KS == 5 && TM == 7 && NW == 7 && rows8) {
+  if (KS == 5 && TM == 7 && NW == 7 && r.rows8) {
     // two stages of NI = 8 (PL = 1: 4) instructions x 8 waves x 1 KB (> the 52 KB staging tile of the slab write)
     constexpr size_t lds8 = (size_t)2 * ((PL * (64 * 14 + 68 * 14) + 511) / 512) * 512 * 16;
     if (PL == 1) {
@@ -955,7 +950,7 @@ static int launch_xwgrad_rows(const XWRowsParams& q, hipStream_t st) {
 #endif
     if (set_max_lds(reinterpret_cast<const void*>(&conv_wgrad_rows8_bf16x3_kernel<0, 1>), (size_t)lds8, attr8_set) != hipSuccess) return WCMC_ERR_LAUNCH;
     if (set_max_lds(reinterpret_cast<const void*>(&conv_wgrad_rows8_bf16x3_kernel<0, 0>), (size_t)lds8, attr80_set) != hipSuccess) return WCMC_ERR_LAUNCH;
-    if (x_env_on("WCMC_WGRAD_ROWS8_XE")) hipLaunchKernelGGL((conv_wgrad_rows8_bf16x3_kernel<0, 1>), grid, dim3(512), lds8, st, q);
+    if (r.xe) hipLaunchKernelGGL((conv_wgrad_rows8_bf16x3_kernel<0, 1>), grid, dim3(512), lds8, st, q);
     else hipLaunchKernelGGL((conv_wgrad_rows8_bf16x3_kernel<0, 0>), grid, dim3(512), lds8, st, q);
     return check_launch("conv2d_wgrad_bf16x3(rows8)");
   }
@@ -979,20 +974,31 @@ static int launch_xwgrad_rows(const XWRowsParams& q, hipStream_t st) {
   return check_launch("conv2d_wgrad_bf16x3(rows)");
 }
 // ks, tm, nw: the filter-row instance of x_plan_wgrad (rTM, rNW); planes: 1 = the hi planes only
-int launch_xwgrad_rows(int ks, int tm, int nw, int planes, const XWRowsParams& q, hipStream_t st) {
+XWRowsPlan x_plan_wgrad_rows(int ks, int tm, int nw, int planes) {
+  XWRowsPlan r;
+  r.ks = ks; r.tm = tm; r.nw = nw; r.pl = planes == 1 ? 1 : 2;
+  // The eight-wave kernel for the two-plane (three-term) launches, the seven-wave one for the one-plane launches of the default
+  // mode: there the seven waves are faster alone (0.311 against 0.295 of the bf16 peak in the eager profile) and beside the other
+  // half of the step (+0.9 % per step, round 4).  WCMC_WGRAD_ROWS8=1 / 0: eight / seven waves for both.
+  const char* r8e = ab_env("WCMC_WGRAD_ROWS8");
+  r.rows8 = (ks == 5 && tm == 7 && nw == 7 && (r8e ? r8e[0] != '0' : r.pl == 2)) ? 1 : 0;
+  r.xe = (r.rows8 && (r.pl == 1 || x_env_on("WCMC_WGRAD_ROWS8_XE"))) ? 1 : 0;      // (the one-plane eight-wave instance exists with XE = 1 only)
+  return r;
+}
+int launch_xwgrad_rows(const XWRowsPlan& r, const XWRowsParams& q, hipStream_t st) {
   int rc = 0;
-  const int key = (planes == 1 ? 1000 : 0) + ks * 100 + tm * 10 + nw;
+  const int key = (r.pl == 1 ? 1000 : 0) + r.ks * 100 + r.tm * 10 + r.nw;
   switch (key) {
-    case 577: rc = launch_xwgrad_rows<5, 7, 7>(q, st); break;
-    case 573: rc = launch_xwgrad_rows<5, 7, 3>(q, st); break;
-    case 388: rc = launch_xwgrad_rows<3, 8, 8>(q, st); break;
-    case 344: rc = launch_xwgrad_rows<3, 4, 4>(q, st); break;
-    case 188: rc = launch_xwgrad_rows<1, 8, 8>(q, st); break;
-    case 1577: rc = launch_xwgrad_rows<5, 7, 7, 1>(q, st); break;
-    case 1573: rc = launch_xwgrad_rows<5, 7, 3, 1>(q, st); break;
-    case 1388: rc = launch_xwgrad_rows<3, 8, 8, 1>(q, st); break;
-    case 1344: rc = launch_xwgrad_rows<3, 4, 4, 1>(q, st); break;
-    case 1188: rc = launch_xwgrad_rows<1, 8, 8, 1>(q, st); break;
+    case 577: rc = launch_xwgrad_rows<5, 7, 7>(r, q, st); break;
+    case 573: rc = launch_xwgrad_rows<5, 7, 3>(r, q, st); break;
+    case 388: rc = launch_xwgrad_rows<3, 8, 8>(r, q, st); break;
+    case 344: rc = launch_xwgrad_rows<3, 4, 4>(r, q, st); break;
+    case 188: rc = launch_xwgrad_rows<1, 8, 8>(r, q, st); break;
+    case 1577: rc = launch_xwgrad_rows<5, 7, 7, 1>(r, q, st); break;
+    case 1573: rc = launch_xwgrad_rows<5, 7, 3, 1>(r, q, st); break;
+    case 1388: rc = launch_xwgrad_rows<3, 8, 8, 1>(r, q, st); break;
+    case 1344: rc = launch_xwgrad_rows<3, 4, 4, 1>(r, q, st); break;
+    case 1188: rc = launch_xwgrad_rows<1, 8, 8, 1>(r, q, st); break;
     default: WCMC_REQUIRE(false, WCMC_ERR_BAD_ARG, "conv2d_wgrad_bf16x3: no filter-row instance for the plan");
   }
   return rc;

@@ -826,78 +826,6 @@ extern "C" int wcmc_conv2d_wgrad_reduce_multi(int n, void* const* workspace, flo
   return check_launch("conv2d_wgrad_reduce_multi");
 }
 
-extern "C" int wcmc_conv2d_igemm_bf16x3(const void* x_split, int N, int H, int W, int Cin, const void* wp,
-                                        const float* bias, float* y, int64_t ysn, int64_t ysh, int64_t ysw,
-                                        void* y_split, int Cout, int ks, int pad, int act, float slope,
-                                        const void* gate_split, int gate_act, float gate_slope,
-                                        float* colsum_partial, const void* gate_mask, void* mask_out,
-                                        int terms, void* stream) {
-  WCMC_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ks > 0 && pad >= 0 && x_split && wp,
-               WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: bad argument");
-  WCMC_REQUIRE(terms >= 1 && terms <= 3, WCMC_ERR_BAD_ARG,
-               "conv2d_igemm_bf16x3: terms must be 3, 2 (x hi plane only; wp packed with mode 2 / 3) or 1 (hi planes of x and W only)");
-  WCMC_REQUIRE(!colsum_partial || y_split, WCMC_ERR_BAD_ARG,
-               "conv2d_igemm_bf16x3: column sums are produced with the split output only");
-  WCMC_REQUIRE((y != nullptr) != (y_split != nullptr), WCMC_ERR_BAD_ARG,
-               "conv2d_igemm_bf16x3: exactly one of y (fp32 view) and y_split must be given");
-  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
-  WCMC_REQUIRE(Ho > 0 && Wo > 0, WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: empty output");
-  WCMC_REQUIRE(aligned16(x_split) && aligned16(wp) && (!y_split || aligned16(y_split)) &&
-                   (!gate_split || aligned16(gate_split)),
-               WCMC_ERR_ALIGNMENT, "conv2d_igemm_bf16x3: split buffers must be 16-byte aligned");
-  WCMC_REQUIRE(!y || nhwc_view_ok(y, ysn, ysh, ysw, Cout), WCMC_ERR_ALIGNMENT,
-               "conv2d_igemm_bf16x3: y violates the NHWC-view contract");
-  WCMC_REQUIRE((!gate_split && !gate_mask && !mask_out) || y_split, WCMC_ERR_BAD_ARG,
-               "conv2d_igemm_bf16x3: a gate / a mask requires the split output geometry");
-  WCMC_REQUIRE(!(gate_split && gate_mask), WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: gate_split and gate_mask are exclusive");
-  XIgemmParams p;
-  p.x = (const u16*)x_split; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cpi = round_up(Cin, 8);
-  p.wp = (const u16*)wp; p.bias = bias;
-  p.yf = y; p.ysn = ysn; p.ysh = ysh; p.ysw = ysw;
-  p.ys = (u16*)y_split; p.Cpo = y_split ? round_up(Cout, 8) : round_up(Cout, 4);
-  p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
-  p.gate = (const u16*)gate_split; p.gate_act = gate_act; p.gate_slope = gate_slope;
-  p.gate_mask = (const unsigned char*)gate_mask; p.mask_out = (unsigned char*)mask_out;
-  p.ks = ks; p.pad = pad; p.act = act; p.slope = slope;
-  const XKPlan q = x_plan_k(Cin, ks, terms <= 2 ? 1 : 2, Cout);
-  p.ap = q.ap;
-  // one term: where the plan grants the hi-plane instance of the 64-pixel 5x5 kernel (the only one with a one-plane weight path);
-  // anywhere else the launch multiplies what the plan's instance multiplies (two or three terms) -- more exact, never less
-  p.wplanes = (terms == 1 && q.ap == 1 && ks == 5 && q.PXS == 80 && x_pick_nt(round_up(Cout, 16) / 16) == 7) ? 1 : 2;
-  p.f16 = 0;
-  p.Kp = p.Cpi; p.Kt = q.Kt; p.Np = round_up(Cout, 16);
-  p.CS = q.CS; p.nslabs = q.nslabs; p.SPS = q.Ks / 32; p.PXS = q.halo ? q.PXS : 0;
-  p.CSl = q.CSl; p.SPSl = q.Ksl / 32;
-  p.tilesY = (Ho + 15) / 16; p.tilesX = (Wo + 15) / 16;
-  p.G = x_colsum_rows(N, Ho, Wo);
-  p.M = (int64_t)N * Ho * Wo;
-  const size_t xb = wcmc_split_elems(N, H, W, Cin) * sizeof(u16), wb = (size_t)p.Np * 2 * p.Kt * sizeof(u16);
-  WCMC_REQUIRE(xb < 0x7ff00000u && wb < 0x7ff00000u, WCMC_ERR_BAD_ARG,
-               "conv2d_igemm_bf16x3: operand larger than 2 GiB (split the batch)");
-  // (the halo kernels push the weight-DMA offsets of stages past the end out of range by adding 2^30: see dma_b)
-  WCMC_REQUIRE(!q.halo || wb < 0x40000000u, WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: packed weights of 1 GiB or more");
-  p.x_bytes = (unsigned)xb; p.wp_bytes = (unsigned)wb;
-  p.colsum = colsum_partial;
-#ifdef WCMC_DEBUG_BUILD
-  {  // timing-only experiments (guide section 7: zero-record descriptors drop one operand's traffic)
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = ab_env("WCMC_DEBUG_DROP"); dbg = e ? atoi(e) : 0; }
-    if (dbg & 1) p.x_bytes = 0;
-    if (dbg & 2) p.wp_bytes = 0;
-  }
-#endif
-  hipStream_t st = (hipStream_t)stream;
-  p.y_bytes = 0; p.m_bytes = 0;
-  p.wp2 = nullptr; p.bias2 = nullptr; p.y2 = nullptr; p.y2sn = p.y2sh = p.y2sw = 0; p.Cout2 = 0; p.act2 = 0; p.Kt2 = 0;
-  p.slope2 = 0.f; p.wp2_bytes = p.y2_bytes = 0;
-  {
-    int ntw = 0, u = 0;
-    if (x_plan_pw(p, &ntw, &u)) return launch_xpw(p, ntw, u, st);
-  }
-  if (x_halo3_ok(p)) return launch_xhalo3(p, st);
-  return launch_xigemm(x_pick_nt(p.Np / 16), p, st);
-}
-
 // ---- the fp16 one-MFMA forward of an un-gated 5x5 output layer ("bf16x321h" mode; profiles/r04_forward_ladder.txt, table "last", rung E)
 static bool x_out_f16_plan(int Cin, int Cout, int ks, XKPlan* q) {
   if (ks != 5 || Cin <= 0 || Cout <= 0) return false;
@@ -921,32 +849,179 @@ extern "C" int wcmc_split_to_f16(const void* x_split, int N, int H, int W, int C
                      (const u16*)x_split, (u16*)out_f16, Cp, total);
   return check_launch("split_to_f16");
 }
+
+// ---- one decision path for the GEMM launches: shape -> parameters -> plan -> launch.  The launch-plan query runs the first three.
+// The scalar half of the entries' argument checks and every field of p that follows from the shape (the pointers are the entry's).
+// gated: a gate, a gate mask or a mask output is asked for; f16: the wcmc_conv2d_out_f16 launch (one fp16 plane, terms = 1).
+static int x_igemm_shape(XIgemmParams& p, const char* who, int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms,
+                         bool split_out, int64_t ysn, int64_t ysh, int64_t ysw, bool gated, bool f16) {
+  WCMC_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ks > 0 && pad >= 0, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  WCMC_REQUIRE(terms >= 1 && terms <= 3, WCMC_ERR_BAD_ARG,
+               "%s: terms must be 3, 2 (x hi plane only; wp packed with mode 2 / 3) or 1 (hi planes of x and W only)", who);
+  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
+  WCMC_REQUIRE(Ho > 0 && Wo > 0, WCMC_ERR_BAD_ARG, "%s: empty output", who);
+  WCMC_REQUIRE(!gated || split_out, WCMC_ERR_BAD_ARG, "%s: a gate / a mask requires the split output geometry", who);
+  XKPlan q;
+  if (f16)
+    WCMC_REQUIRE(x_out_f16_plan(Cin, Cout, ks, &q), WCMC_ERR_BAD_ARG,
+                 "%s: no fp16 instance for this shape (ask wcmc_conv2d_out_f16_supported; 5x5, cout blocks of seven tiles)", who);
+  else
+    q = x_plan_k(Cin, ks, terms <= 2 ? 1 : 2, Cout);
+  p = XIgemmParams{};
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cpi = round_up(Cin, 8);
+  p.ysn = ysn; p.ysh = ysh; p.ysw = ysw;
+  p.Cpo = split_out ? round_up(Cout, 8) : round_up(Cout, 4);
+  p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
+  p.ks = ks; p.pad = pad;
+  p.ap = f16 ? 1 : q.ap;
+  // one term: where the plan grants the hi-plane instance of the 64-pixel 5x5 kernel (the only one with a one-plane weight path);
+  // anywhere else the launch multiplies what the plan's instance multiplies (two or three terms) -- more exact, never less
+  p.wplanes = (f16 || (terms == 1 && q.ap == 1 && ks == 5 && q.PXS == 80 && x_pick_nt(round_up(Cout, 16) / 16) == 7)) ? 1 : 2;
+  p.f16 = f16 ? 1 : 0;
+  p.Kp = p.Cpi; p.Kt = q.Kt; p.Np = round_up(Cout, 16);
+  p.CS = q.CS; p.nslabs = q.nslabs; p.SPS = q.Ks / 32; p.PXS = q.halo ? q.PXS : 0;
+  p.CSl = q.CSl; p.SPSl = q.Ksl / 32;
+  p.tilesY = (Ho + 15) / 16; p.tilesX = (Wo + 15) / 16;
+  p.G = x_colsum_rows(N, Ho, Wo);
+  p.M = (int64_t)N * Ho * Wo;
+  const size_t xb = (f16 ? (size_t)N * H * W * p.Cpi : wcmc_split_elems(N, H, W, Cin)) * sizeof(u16), wb = (size_t)p.Np * 2 * p.Kt * sizeof(u16);
+  WCMC_REQUIRE(xb < 0x7ff00000u && wb < 0x7ff00000u, WCMC_ERR_BAD_ARG, "%s: operand larger than 2 GiB (split the batch)", who);
+  // (the halo kernels push the weight-DMA offsets of stages past the end out of range by adding 2^30: see dma_b)
+  WCMC_REQUIRE(!q.halo || wb < 0x40000000u, WCMC_ERR_BAD_ARG, "%s: packed weights of 1 GiB or more", who);
+  p.x_bytes = (unsigned)xb; p.wp_bytes = (unsigned)wb;
+  return 0;
+}
+// Which family runs the launch and that family's plan (bf16x3_common.h).  Reads of p only: which output and whether a gate tensor
+// is given are asked of the pointers being null or not.
+struct XConvPlan {
+  enum { PW, HALO3, IGEMM, HALO, HALO64 } family;
+  XPwPlan pw; XHalo3Plan h3; XIgemmPlan ig; XHaloPlan halo; XHalo64Plan h64;
+};
+static int x_plan_conv(const XIgemmParams& p, XConvPlan* c) {
+  const int nt = x_pick_nt(p.Np / 16);
+  if (x_plan_pw(p, &c->pw)) c->family = XConvPlan::PW;
+  else if (x_halo3_ok(p)) { c->family = XConvPlan::HALO3; c->h3 = x_plan_halo3(p); }
+  else if (!p.PXS) { c->family = XConvPlan::IGEMM; c->ig = x_plan_igemm(nt, p); }
+  else if (x_halo_is64(p)) { c->family = XConvPlan::HALO64; c->h64 = x_plan_halo64(nt, p); }
+  else { c->family = XConvPlan::HALO; return x_plan_halo(nt, p, &c->halo); }
+  return 0;
+}
+static int x_launch_conv(const XConvPlan& c, XIgemmParams& p, hipStream_t st) {
+  switch (c.family) {
+    case XConvPlan::PW: return launch_xpw(p, c.pw, st);
+    case XConvPlan::HALO3: return launch_xhalo3(c.h3, p, st);
+    case XConvPlan::IGEMM: return launch_xigemm(c.ig, p, st);
+    case XConvPlan::HALO64: return launch_xhalo64(c.h64, p, st);
+    default: return launch_xhalo(c.halo, p, st);
+  }
+}
+// Profiler class (the vocabulary of bench.py: a class that names ONE kernel instance there is given to that instance only, every
+// other kernel is "conv_igemm") and the kernel as rocprofv3 prints it, every template argument written out.
+static int x_name_conv(const XConvPlan& c, const XIgemmParams& p, char* cls, char* kernel, size_t len) {      // returns the longer string's length
+  const char* k = "conv_igemm";
+  int kn = 0, cn = 0;
+  switch (c.family) {
+    case XConvPlan::PW:
+      k = "conv_pw";
+      kn = snprintf(kernel, len, "conv_pw_bf16x3_kernel<%d, %d, %s, 0>", c.pw.ntw, c.pw.u, p.ys ? "true" : "false");
+      break;
+    case XConvPlan::HALO3:
+      k = c.h3.ap == 2 ? "conv_halo3" : "conv_halo3_x2";
+      kn = snprintf(kernel, len, "conv_halo3_bf16x3_kernel<%d, %d, 2, 0>", c.h3.ap, c.h3.spt);
+      break;
+    case XConvPlan::IGEMM:
+      kn = snprintf(kernel, len, "conv_igemm_bf16x3_kernel<%d, %s, %s, 0>", c.ig.nt, c.ig.padded ? "true" : "false", c.ig.dbuf ? "true" : "false");
+      break;
+    case XConvPlan::HALO:
+      if (c.halo.nt == 7 && c.halo.th == 8 && c.halo.ap == 2) k = "conv_halo7";
+      kn = snprintf(kernel, len, "conv_halo_bf16x3_kernel<%d, %d, 16, 0, %d, %d>", c.halo.nt, c.halo.th, c.halo.nb, c.halo.ap);
+      break;
+    case XConvPlan::HALO64: {
+      const XHalo64Plan& h = c.h64;
+      if (h.nt == 7 && h.nb == 2 && h.pt == 3 && h.pxst == 160) k = "conv_halo64_cs32";
+      else if (h.nt == 7 && h.nb == 3 && h.pxst == 80) {
+        cn = snprintf(cls, len, "conv_halo64_pt%d%s", h.pt, h.f16 ? "_h1" : h.wp == 1 ? "_x1" : h.ap == 1 ? "_x2" : "");
+        k = nullptr;
+      }
+      kn = snprintf(kernel, len, "conv_halo64_bf16x3_kernel<%d, %d, %d, 0, %d, %d, %d, %d>", h.nt, h.nb, h.pt, h.pxst, h.ap, h.wp, h.f16);
+      break;
+    }
+  }
+  if (k) cn = snprintf(cls, len, "%s", k);
+  return cn > kn ? cn : kn;
+}
+
+extern "C" int wcmc_conv2d_launch_plan_bf16x3(int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms, int split_out,
+                                              int64_t ysn, int64_t ysh, int64_t ysw, int gate_tensor, int out_f16,
+                                              char* cls, char* kernel, size_t len) {
+  const char* who = "conv2d_launch_plan_bf16x3";
+  WCMC_REQUIRE(cls && kernel && len > 0, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  WCMC_REQUIRE(!out_f16 || (!split_out && !gate_tensor), WCMC_ERR_BAD_ARG, "%s: the fp16 launch writes an fp32 view, un-gated", who);
+  XIgemmParams p;
+  if (const int rc = x_igemm_shape(p, who, N, H, W, Cin, Cout, ks, pad, out_f16 ? 1 : terms, split_out != 0, ysn, ysh, ysw,
+                                   gate_tensor != 0, out_f16 != 0)) return rc;
+  static const u16 given = 0;              // (never read: the plans ask only whether a pointer is null)
+  if (split_out) p.ys = const_cast<u16*>(&given); else p.yf = reinterpret_cast<float*>(const_cast<u16*>(&given));
+  if (gate_tensor) p.gate = &given;
+  XConvPlan c;
+  if (const int rc = x_plan_conv(p, &c)) return rc;
+  WCMC_REQUIRE((size_t)x_name_conv(c, p, cls, kernel, len) < len, WCMC_ERR_BAD_ARG, "%s: buffers of %zu bytes are too short", who, len);
+  return 0;
+}
+
+extern "C" int wcmc_conv2d_igemm_bf16x3(const void* x_split, int N, int H, int W, int Cin, const void* wp,
+                                        const float* bias, float* y, int64_t ysn, int64_t ysh, int64_t ysw,
+                                        void* y_split, int Cout, int ks, int pad, int act, float slope,
+                                        const void* gate_split, int gate_act, float gate_slope,
+                                        float* colsum_partial, const void* gate_mask, void* mask_out,
+                                        int terms, void* stream) {
+  const char* who = "conv2d_igemm_bf16x3";
+  WCMC_REQUIRE(x_split && wp, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  WCMC_REQUIRE(!colsum_partial || y_split, WCMC_ERR_BAD_ARG,
+               "conv2d_igemm_bf16x3: column sums are produced with the split output only");
+  WCMC_REQUIRE((y != nullptr) != (y_split != nullptr), WCMC_ERR_BAD_ARG,
+               "conv2d_igemm_bf16x3: exactly one of y (fp32 view) and y_split must be given");
+  XIgemmParams p;
+  if (const int rc = x_igemm_shape(p, who, N, H, W, Cin, Cout, ks, pad, terms, y_split != nullptr, ysn, ysh, ysw,
+                                   gate_split || gate_mask || mask_out, false)) return rc;
+  WCMC_REQUIRE(aligned16(x_split) && aligned16(wp) && (!y_split || aligned16(y_split)) &&
+                   (!gate_split || aligned16(gate_split)),
+               WCMC_ERR_ALIGNMENT, "conv2d_igemm_bf16x3: split buffers must be 16-byte aligned");
+  WCMC_REQUIRE(!y || nhwc_view_ok(y, ysn, ysh, ysw, Cout), WCMC_ERR_ALIGNMENT,
+               "conv2d_igemm_bf16x3: y violates the NHWC-view contract");
+  WCMC_REQUIRE(!(gate_split && gate_mask), WCMC_ERR_BAD_ARG, "conv2d_igemm_bf16x3: gate_split and gate_mask are exclusive");
+  p.x = (const u16*)x_split; p.wp = (const u16*)wp; p.bias = bias;
+  p.yf = y; p.ys = (u16*)y_split;
+  p.gate = (const u16*)gate_split; p.gate_act = gate_act; p.gate_slope = gate_slope;
+  p.gate_mask = (const unsigned char*)gate_mask; p.mask_out = (unsigned char*)mask_out;
+  p.act = act; p.slope = slope;
+  p.colsum = colsum_partial;
+#ifdef WCMC_DEBUG_BUILD
+  {  // timing-only experiments (guide section 7: zero-record descriptors drop one operand's traffic)
+    static int dbg = -1;
+    if (dbg < 0) { const char* e = ab_env("WCMC_DEBUG_DROP"); dbg = e ? atoi(e) : 0; }
+    if (dbg & 1) p.x_bytes = 0;
+    if (dbg & 2) p.wp_bytes = 0;
+  }
+#endif
+  XConvPlan c;
+  if (const int rc = x_plan_conv(p, &c)) return rc;
+  return x_launch_conv(c, p, (hipStream_t)stream);
+}
+
 extern "C" int wcmc_conv2d_out_f16(const void* x_f16, int N, int H, int W, int Cin, const void* wp_f16, const float* bias, float* y,
                                    int64_t ysn, int64_t ysh, int64_t ysw, int Cout, int ks, int pad, void* stream) {
-  WCMC_REQUIRE(x_f16 && wp_f16 && y && N > 0 && H > 0 && W > 0 && pad >= 0, WCMC_ERR_BAD_ARG, "conv2d_out_f16: bad argument");
-  XKPlan q;
-  WCMC_REQUIRE(x_out_f16_plan(Cin, Cout, ks, &q), WCMC_ERR_BAD_ARG,
-               "conv2d_out_f16: no fp16 instance for this shape (ask wcmc_conv2d_out_f16_supported; 5x5, cout blocks of seven tiles)");
-  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
-  WCMC_REQUIRE(Ho > 0 && Wo > 0, WCMC_ERR_BAD_ARG, "conv2d_out_f16: empty output");
+  const char* who = "conv2d_out_f16";
+  WCMC_REQUIRE(x_f16 && wp_f16 && y, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  XIgemmParams p;
+  if (const int rc = x_igemm_shape(p, who, N, H, W, Cin, Cout, ks, pad, 1, false, ysn, ysh, ysw, false, true)) return rc;
   WCMC_REQUIRE(aligned16(x_f16) && aligned16(wp_f16) && nhwc_view_ok(y, ysn, ysh, ysw, Cout), WCMC_ERR_ALIGNMENT,
                "conv2d_out_f16: unaligned operand or y violates the NHWC-view contract");
-  XIgemmParams p = {};
-  p.x = (const u16*)x_f16; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cpi = round_up(Cin, 8);
-  p.wp = (const u16*)wp_f16; p.bias = bias;
-  p.yf = y; p.ysn = ysn; p.ysh = ysh; p.ysw = ysw; p.ys = nullptr; p.Cpo = round_up(Cout, 4);
-  p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
-  p.gate = nullptr; p.gate_act = WCMC_ACT_LINEAR; p.gate_slope = 0.f; p.gate_mask = nullptr; p.mask_out = nullptr;
-  p.ks = ks; p.pad = pad; p.act = WCMC_ACT_LINEAR; p.slope = 0.f;
-  p.ap = 1; p.wplanes = 1; p.f16 = 1;
-  p.Kp = p.Cpi; p.Kt = q.Kt; p.Np = round_up(Cout, 16);
-  p.CS = q.CS; p.nslabs = q.nslabs; p.SPS = q.Ks / 32; p.PXS = q.PXS; p.CSl = q.CSl; p.SPSl = q.Ksl / 32;
-  p.tilesY = (Ho + 15) / 16; p.tilesX = (Wo + 15) / 16;
-  p.G = x_colsum_rows(N, Ho, Wo); p.M = (int64_t)N * Ho * Wo;
-  const size_t xb = (size_t)N * H * W * p.Cpi * sizeof(u16), wb = (size_t)p.Np * 2 * p.Kt * sizeof(u16);
-  WCMC_REQUIRE(xb < 0x7ff00000u && wb < 0x40000000u, WCMC_ERR_BAD_ARG, "conv2d_out_f16: operand too large (split the batch)");
-  p.x_bytes = (unsigned)xb; p.wp_bytes = (unsigned)wb; p.colsum = nullptr;
-  return launch_xigemm(7, p, (hipStream_t)stream);
+  p.x = (const u16*)x_f16; p.wp = (const u16*)wp_f16; p.bias = bias; p.yf = y;
+  p.gate_act = WCMC_ACT_LINEAR; p.act = WCMC_ACT_LINEAR;
+  XConvPlan c;
+  if (const int rc = x_plan_conv(p, &c)) return rc;
+  return x_launch_conv(c, p, (hipStream_t)stream);
 }
 
 static bool x_pair_enabled() {
@@ -1027,34 +1102,61 @@ extern "C" size_t wcmc_conv2d_wgrad_bf16x3_workspace_bytes(int N, int Ho, int Wo
   return b3 > b1 ? b3 : b1;                              // (enough for either number of terms)
 }
 
+// The scalar half of wcmc_conv2d_wgrad_bf16x3's argument checks, the plan and every field of p that follows from the shape
+// (shared with the launch-plan query; the pointers are the entry's).
+static int x_wgrad_shape(XWgradParams& p, XWgradPlan& pl, const char* who, int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms) {
+  WCMC_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ks > 0 && pad >= 0, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  WCMC_REQUIRE(terms == 3 || terms == 1, WCMC_ERR_BAD_ARG, "%s: terms must be 3 (hi*hi + hi*lo + lo*hi) or 1 (the hi planes only)", who);
+  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
+  WCMC_REQUIRE(Ho > 0 && Wo > 0, WCMC_ERR_BAD_ARG, "%s: empty output", who);
+  pl = x_plan_wgrad(N, Ho, Wo, Cout, Cin, ks, terms);
+  p = XWgradParams{};
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cpi = round_up(Cin, 8);
+  p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.Cpo = round_up(Cout, 8);
+  p.ks = ks; p.pad = pad; p.S = pl.S; p.M = (int64_t)N * Ho * Wo;
+  p.pix_per_split = pl.pix_per_split; p.Np = pl.Np; p.Cq = pl.Cq; p.coBlocks = pl.coBlocks; p.ciBlocks = pl.ciBlocks;
+  const size_t xb = wcmc_split_elems(N, H, W, Cin) * sizeof(u16), yb = wcmc_split_elems(N, Ho, Wo, Cout) * sizeof(u16);
+  WCMC_REQUIRE(xb < 0x7ff00000u && yb < 0x7ff00000u, WCMC_ERR_BAD_ARG, "%s: operand larger than 2 GiB (split the batch)", who);
+  p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)yb;
+  p.xps = 4 * p.Cpi; p.yps = 4 * p.Cpo;
+  return 0;
+}
+
+// The GEMM launch of wcmc_conv2d_wgrad_bf16x3 (phases 0 and 1): "conv_wgrad_rows" is the 5x5 filter-row kernel of seven by seven
+// channel tiles (either wave count), "conv_wgrad" every other kernel.
+extern "C" int wcmc_conv2d_wgrad_launch_plan_bf16x3(int N, int H, int W, int Cin, int Cout, int ks, int pad, int terms,
+                                                    char* cls, char* kernel, size_t len) {
+  const char* who = "conv2d_wgrad_launch_plan_bf16x3";
+  WCMC_REQUIRE(cls && kernel && len > 0, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  XWgradParams p;
+  XWgradPlan pl;
+  if (const int rc = x_wgrad_shape(p, pl, who, N, H, W, Cin, Cout, ks, pad, terms)) return rc;
+  const XWRowsPlan r = x_plan_wgrad_rows(ks, pl.rTM, pl.rNW, terms == 1 ? 1 : 2);
+  const int cn = snprintf(cls, len, "%s", (pl.rows && ks == 5 && pl.rTM == 7 && pl.rNW == 7) ? "conv_wgrad_rows" : "conv_wgrad");
+  const int kn = pl.rows && r.rows8 ? snprintf(kernel, len, "conv_wgrad_rows8_bf16x3_kernel<0, %d, %d>", r.xe, r.pl)
+                 : pl.rows ? snprintf(kernel, len, "conv_wgrad_rows_bf16x3_kernel<%d, %d, %d, 0, %d>", r.ks, r.tm, r.nw, r.pl)
+                           : snprintf(kernel, len, "conv_wgrad_bf16x3_kernel<%d, %d>", pl.TM, r.pl);
+  WCMC_REQUIRE((size_t)(cn > kn ? cn : kn) < len, WCMC_ERR_BAD_ARG, "%s: buffers of %zu bytes are too short", who, len);
+  return 0;
+}
+
 extern "C" int wcmc_conv2d_wgrad_bf16x3(const void* x_split, int N, int H, int W, int Cin, const void* dy_split,
                                         int Cout, int ks, int pad, float* dw, float* db, void* workspace,
                                         size_t workspace_bytes, int phase, const float* dy_colsum_partial, int terms,
                                         void* stream) {
-  WCMC_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ks > 0 && pad >= 0 && dw && workspace &&
-                   x_split && dy_split,
-               WCMC_ERR_BAD_ARG, "conv2d_wgrad_bf16x3: bad argument");
-  WCMC_REQUIRE(terms == 3 || terms == 1, WCMC_ERR_BAD_ARG,
-               "conv2d_wgrad_bf16x3: terms must be 3 (hi*hi + hi*lo + lo*hi) or 1 (the hi planes only)");
-  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
-  WCMC_REQUIRE(Ho > 0 && Wo > 0, WCMC_ERR_BAD_ARG, "conv2d_wgrad_bf16x3: empty output");
+  const char* who = "conv2d_wgrad_bf16x3";
+  WCMC_REQUIRE(dw && workspace && x_split && dy_split, WCMC_ERR_BAD_ARG, "%s: bad argument", who);
+  XWgradParams p;
+  XWgradPlan pl;
+  if (const int rc = x_wgrad_shape(p, pl, who, N, H, W, Cin, Cout, ks, pad, terms)) return rc;
+  const int Ho = p.Ho, Wo = p.Wo;
   WCMC_REQUIRE(aligned16(x_split) && aligned16(dy_split), WCMC_ERR_ALIGNMENT,
                "conv2d_wgrad_bf16x3: split buffers must be 16-byte aligned");
-  const XWgradPlan pl = x_plan_wgrad(N, Ho, Wo, Cout, Cin, ks, terms);
   WCMC_REQUIRE(workspace_bytes >= pl.bytes && aligned16(workspace), WCMC_ERR_WORKSPACE,
                "conv2d_wgrad_bf16x3: workspace %zu < %zu bytes (or unaligned)", workspace_bytes, pl.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  XWgradParams p;
-  p.x = (const u16*)x_split; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cpi = round_up(Cin, 8);
-  p.dy = (const u16*)dy_split; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.Cpo = round_up(Cout, 8);
-  p.ks = ks; p.pad = pad; p.slabs = (float*)workspace; p.S = pl.S; p.M = (int64_t)N * Ho * Wo;
-  p.pix_per_split = pl.pix_per_split; p.Np = pl.Np; p.Cq = pl.Cq; p.coBlocks = pl.coBlocks; p.ciBlocks = pl.ciBlocks;
-  const size_t xb = wcmc_split_elems(N, H, W, Cin) * sizeof(u16), yb = wcmc_split_elems(N, Ho, Wo, Cout) * sizeof(u16);
-  WCMC_REQUIRE(xb < 0x7ff00000u && yb < 0x7ff00000u, WCMC_ERR_BAD_ARG,
-               "conv2d_wgrad_bf16x3: operand larger than 2 GiB (split the batch)");
-  p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)yb;
-  p.xps = 4 * p.Cpi; p.yps = 4 * p.Cpo;
   WCMC_REQUIRE(phase >= 0 && phase <= 2, WCMC_ERR_BAD_ARG, "conv2d_wgrad_bf16x3: phase must be 0, 1 or 2");
+  hipStream_t st = (hipStream_t)stream;
+  p.x = (const u16*)x_split; p.dy = (const u16*)dy_split; p.slabs = (float*)workspace;
   int rc = 0;
   if (phase != 2 && pl.rows) {
     XWRowsParams q;
@@ -1064,7 +1166,7 @@ extern "C" int wcmc_conv2d_wgrad_bf16x3(const void* x_split, int N, int H, int W
     q.pad = pad; q.slabs = p.slabs; q.S = pl.S; q.rps = pl.rps; q.R = pl.R; q.Np = pl.Np; q.Cq = pl.Cq;
     q.coBlocks = pl.coBlocks; q.ciBlocks = pl.ciBlocks; q.x_bytes = p.x_bytes; q.dy_bytes = p.dy_bytes;
     q.xps = p.xps; q.yps = p.yps;
-    rc = launch_xwgrad_rows(ks, pl.rTM, pl.rNW, terms == 1 ? 1 : 2, q, st);
+    rc = launch_xwgrad_rows(x_plan_wgrad_rows(ks, pl.rTM, pl.rNW, terms == 1 ? 1 : 2), q, st);
   } else if (phase != 2) {
     rc = launch_xwgrad(pl.TM, terms == 1 ? 1 : 2, p, st);
   }

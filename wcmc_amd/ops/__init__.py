@@ -142,7 +142,7 @@ def out_layer_terms(ks, act):
 # ---------------------------------------------------------------------------------------------------------------- the modules
 # Every name each module defines, in dependency order.  (The modules reach the names above through ``_sw``, inside functions only.)
 from ._base import (ACT, LEAKY_SLOPE, set_profiler, _Timed, _ptr, _stream, _need_cuda, nhwc_empty, is_nhwc_view, _v,  # noqa: E402,F401
-                    to_nhwc_raw, from_nhwc_raw, _ToNHWC, as_nhwc, _as_nhwc_nograd, _igemm_class, _wgrad_class)
+                    to_nhwc_raw, from_nhwc_raw, _ToNHWC, as_nhwc, _as_nhwc_nograd, conv_launch_plan, wgrad_launch_plan, _timed_conv)
 from .streams import (_SIDE_STREAMS, _side_stream, _BRANCH_STREAMS, branch_stream, _step_streams, fork_all_streams,  # noqa: E402,F401
                       join_all_streams, _STREAM_PAIRS, _spin_ms, concurrent_stream_pair, on_branch)
 from .conv_fp32 import (_pack, conv2d_raw, conv2d_wgrad_raw, act_backward_raw, _ConvChain)  # noqa: E402,F401

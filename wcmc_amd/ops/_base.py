@@ -1,5 +1,5 @@
-"""What every module of the package stands on: activation codes, the per-launch profiler hook and the profiler classes of the conv
-launches, pointer / stream / stride helpers and the NHWC views."""
+"""What every module of the package stands on: activation codes, the per-launch profiler hook and the launch-plan queries that name
+the conv launches' profiler classes, pointer / stream / stride helpers and the NHWC views."""
 import ctypes
 
 import torch
@@ -110,44 +110,31 @@ def _as_nhwc_nograd(g):
     return g if is_nhwc_view(g) else to_nhwc_raw(g)
 
 
-def _igemm_class(cin, cout, ks, dims=None, terms=3):
-    """Profiler class of a split-bf16 GEMM launch = the kernel the library's plan picks for it
-    (csrc/conv_bf16x3.hip: x_plan_k, x_pick_nt; csrc/bf16x3_pw.hip: x_plan_pw; csrc/bf16x3_halo3.hip: x_halo3_ok; csrc/bf16x3_halo64.hip: launch_xhalo64), so that a class average is one kernel's average.
-    dims = (n, ho, wo) of the output selects between the two tile heights of the 5x5 kernel; terms = 2 (the data gradient of
-    the default mode) runs the AP = 1 instances where the plan grants them: classes with the suffix "_x2"; terms = 1 (the output
-    layers' forward of the default mode): "_x1"."""
-    tiles = (cout + 15) // 16
-    nt = min((7, 4, 2, 1), key=lambda t: (-(-tiles // t)) * (t + 2))
-    halo = 3 <= ks <= 5 and (cin + 7) // 8 * 8 >= 32
-    if ks == 1 and ((cin + 7) // 8 * 8, cout) in ((64, 64), (40, 64), (128, 128), (8, 128)):
-        return "conv_pw"                    # x_plan_pw: the persistent pointwise kernel (HBM-bound class)
-    if halo and ks == 3 and (cout + 15) // 16 * 16 % 64 == 0:
-        # conv_halo3_bf16x3_kernel (x_halo3_ok): the U-Net's 3x3 layers -- slabs of exactly 64 channels (three terms) or of 64 / 128
-        # channels of the hi plane (two terms: "_x2")
-        kp3 = (cin + 7) // 8 * 8
-        if terms >= 3 and kp3 % 64 == 0:
-            return "conv_halo3"
-        if terms <= 2 and (kp3 == 64 or kp3 % 128 == 0):
-            return "conv_halo3_x2"
-    if not (halo and nt == 7 and ks == 5):
-        return "conv_igemm"
-    if dims is None:
-        return "conv_halo7"                 # (the fp32 path's 5x5 class)
-    n, ho, wo = dims                        # conv_halo64_bf16x3_kernel<7, NB, PT>: 16x16 tiles (PT = 4; also the mixed 16 / 12 heights) or 12x16 (PT = 3)
-    kp = (cin + 7) // 8 * 8
-    x2 = terms <= 2 and kp % 32 != 24      # x_plan_k grants ap = 1 (32-channel slabs, 80 B)
-    x1 = x2 and terms == 1              # ... and the one-plane weight path: <7, 3, PT, 0, 80, 1, 1>, suffix "_x1"
-    if not x2 and kp >= 256 and kp % 32 == 0:
-        return "conv_halo64_cs32"           # 32-channel slabs: <7, 2, 3> (two weight stages, 12x16 tiles)
-    gy = -(-tiles // nt)
-    rounds = lambda th: -(-(n * (-(-wo // 16)) * (-(-ho // th)) * gy) // 512) * th
-    pt3 = rounds(12) < rounds(16)
-    # round 6: where 16 does not divide ho but a rows of 16 + b >= 1 rows of 12 cover it exactly, the 16-row instance runs (mixed tile heights)
-    if ho % 16 != 0 and any((ho - 12 * b) % 16 == 0 for b in range(1, (ho - 1) // 12 + 1)):
-        pt3 = False
-    return ("conv_halo64_pt3" if pt3 else "conv_halo64_pt4") + ("_x1" if x1 else "_x2" if x2 else "")
+def conv_launch_plan(n, h, w, cin, cout, ks, pad, terms=3, out_split=True, ystrides=(0, 0, 0), gate=False, f16=False):
+    """(profiler class, kernel instance as rocprofv3 prints it) of the launch ``wcmc_conv2d_igemm_bf16x3`` -- f16: ``wcmc_conv2d_out_f16`` --
+    would run for these arguments: asked of the library's own launch plan (``wcmc_conv2d_launch_plan_bf16x3``), which touches no device.
+    ystrides: (sn, sh, sw) of the fp32 output view when not out_split; gate: a gate TENSOR is given (a bit mask is not one)."""
+    cls, ker = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
+    check(lib().wcmc_conv2d_launch_plan_bf16x3(n, h, w, cin, cout, ks, pad, terms, int(out_split), *ystrides, int(gate), int(f16),
+                                               cls, ker, 128), "conv2d_launch_plan_bf16x3")
+    return cls.value.decode(), ker.value.decode()
 
 
-def _wgrad_class(n, ho, cin, cout, ks):
-    rows = ks == 5 and (cin + 15) // 16 == 7 and ((cout + 15) // 16) % 7 == 0 and n * ho >= 64
-    return "conv_wgrad_rows" if rows else "conv_wgrad"
+def wgrad_launch_plan(n, h, w, cin, cout, ks, pad, terms=3):
+    """(profiler class, kernel instance) of the GEMM launch of ``wcmc_conv2d_wgrad_bf16x3``, as ``conv_launch_plan``."""
+    cls, ker = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
+    check(lib().wcmc_conv2d_wgrad_launch_plan_bf16x3(n, h, w, cin, cout, ks, pad, terms, cls, ker, 128), "conv2d_wgrad_launch_plan_bf16x3")
+    return cls.value.decode(), ker.value.decode()
+
+
+def _timed_conv(dims, cout, ks, pad, terms, yf, gate, f16=False):
+    """The profiler bracket of one GEMM launch, under the class the library's launch plan names for it (yf: the fp32 output view,
+    None for a split output; gate: a gate tensor is given).  Without a profiler nothing is classified."""
+    if _sw._PROFILER is None:
+        return _Timed(None, 0.0, "flop")
+    n, cin, h, w = dims
+    pix = min((h + 2 * pad - ks + 1) * (w + 2 * pad - ks + 1), h * w)
+    cls = conv_launch_plan(n, h, w, cin, cout, ks, pad, terms, yf is None, (0, 0, 0) if yf is None else _v(yf)[1:], gate, f16)[0]
+    if cls == "conv_pw":    # algorithmic bytes: the split input and the split / fp32 output, 4 B per channel and pixel
+        return _Timed(cls, 4.0 * n * pix * ((cin + 7) // 8 * 8 + cout), "byte")
+    return _Timed(cls, 2.0 * n * pix * cout * cin * ks * ks, "flop")

@@ -3,7 +3,7 @@ import torch
 
 from .. import ops as _sw          # the package itself: switches and rebound state are read there, when a function runs
 from .._lib import check, lib
-from ._base import ACT, LEAKY_SLOPE, _Timed, _as_nhwc_nograd, _igemm_class, _need_cuda, _ptr, _stream, _v, nhwc_empty
+from ._base import ACT, LEAKY_SLOPE, _Timed, _as_nhwc_nograd, _need_cuda, _ptr, _stream, _v, nhwc_empty
 from .streams import _side_stream
 
 
@@ -20,6 +20,19 @@ def _pack(weight, mode):
     return wp
 
 
+def _layer_label(cin, cout, ks):
+    """Profiler LABEL of a layer shape in the exact-fp32 mode.  The fp32 library has one GEMM kernel: these strings name no kernel,
+    they sort the launches by the shapes the split-bf16 classes of the same names cover (1x1 PathNet pairs, the U-Net's 3x3
+    layers of 64-channel slabs, KPCN's 5x5 layers with seven cout tiles per block), so that the two modes' tables read side by side."""
+    kp, tiles = (cin + 7) // 8 * 8, (cout + 15) // 16
+    if ks == 1 and (kp, cout) in ((64, 64), (40, 64), (128, 128), (8, 128)):
+        return "conv_pw"
+    if ks == 3 and kp >= 32 and tiles % 4 == 0 and kp % 64 == 0:
+        return "conv_halo3"
+    seven = min((7, 4, 2, 1), key=lambda t: (-(-tiles // t)) * (t + 2)) == 7
+    return "conv_halo7" if ks == 5 and kp >= 32 and seven else "conv_igemm"
+
+
 def conv2d_raw(x, wp, bias, cout, ks, pad, act, gate=None, gate_act="linear", out=None):
     """One implicit-GEMM launch: out = act(conv(x) + bias) [* act'(gate)]."""
     n, cin, h, w = x.shape
@@ -29,7 +42,7 @@ def conv2d_raw(x, wp, bias, cout, ks, pad, act, gate=None, gate_act="linear", ou
     g = _v(gate) if gate is not None else (_ptr(None), 0, 0, 0)
     # algorithmic FLOPs: 2 * pixels * Cout * Cin * ks^2 of the (smaller) valid-conv side
     pix = min(ho * wo, h * w)
-    with _Timed(_igemm_class(cin, cout, ks), 2.0 * n * pix * cout * cin * ks * ks, "flop"):
+    with _Timed(_layer_label(cin, cout, ks), 2.0 * n * pix * cout * cin * ks * ks, "flop"):
         check(lib().wcmc_conv2d_igemm(*_v(x), n, h, w, cin, _ptr(wp), _ptr(bias), *_v(out), cout, ks, pad,
                                       ACT[act], LEAKY_SLOPE, *g, ACT[gate_act], LEAKY_SLOPE, _stream()),
               "conv2d_igemm")

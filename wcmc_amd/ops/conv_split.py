@@ -6,7 +6,7 @@ import torch
 
 from .. import ops as _sw          # the package itself: switches and rebound state are read there, when a function runs
 from .._lib import check, lib
-from ._base import (ACT, LEAKY_SLOPE, _Timed, _as_nhwc_nograd, _igemm_class, _need_cuda, _ptr, _stream, _v, _wgrad_class,
+from ._base import (ACT, LEAKY_SLOPE, _Timed, _as_nhwc_nograd, _need_cuda, _ptr, _stream, _timed_conv, _v, wgrad_launch_plan,
                     as_nhwc, nhwc_empty)
 from .conv_fp32 import _ConvChain
 from .grads import _flushed_by_consumer, _on_side_stream, _sink_ex
@@ -169,19 +169,13 @@ def conv2d_x_raw(xs, dims, wp, bias, cout, ks, pad, act, out_split, gate=None, g
         yf = nhwc_empty(n, cout, ho, wo, dev) if out is None else out
         assert tuple(yf.shape) == (n, cout, ho, wo)
         ysp, yv = None, _v(yf)
-    pix = min(ho * wo, h * w)
     part = None
     if colsum:
         part = torch.empty(lib().wcmc_conv2d_igemm_colsum_elems(n, ho, wo, cout), device=dev, dtype=torch.float32)
     mask = None
     if mask_out:
         mask = torch.empty(n * ho * wo * ((cout + 7) // 8), device=dev, dtype=torch.uint8)
-    cls = _igemm_class(cin, cout, ks, (n, ho, wo), terms) if pad == 0 or ks > 1 else "conv_igemm"
-    if cls == "conv_pw":    # algorithmic bytes: the split input and the split / fp32 output, 4 B per channel and pixel
-        work = (4.0 * n * pix * ((cin + 7) // 8 * 8 + cout), "byte")
-    else:
-        work = (2.0 * n * pix * cout * cin * ks * ks, "flop")
-    with _Timed(cls, *work):
+    with _timed_conv(dims, cout, ks, pad, terms, yf, gate is not None):
         check(lib().wcmc_conv2d_igemm_bf16x3(_ptr(xs), n, h, w, cin, _ptr(wp), _ptr(bias), *yv, _ptr(ysp), cout,
                                              ks, pad, ACT[act], LEAKY_SLOPE, _ptr(gate), ACT[gate_act], LEAKY_SLOPE,
                                              _ptr(part), _ptr(gate_mask), _ptr(mask), terms, _stream()), "conv2d_igemm_bf16x3")
@@ -198,7 +192,7 @@ def conv2d_out_f16_raw(xs, dims, wp16, bias, cout, ks, pad):
     x16 = torch.empty(lib().wcmc_split_to_f16_elems(n, h, w, cin), device=xs.device, dtype=torch.int16)
     check(lib().wcmc_split_to_f16(_ptr(xs), n, h, w, cin, _ptr(x16), _stream()), "split_to_f16")
     y = nhwc_empty(n, cout, ho, wo, xs.device)
-    with _Timed(_igemm_class(cin, cout, ks, (n, ho, wo), 1).replace("_x1", "_h1"), 2.0 * n * min(ho * wo, h * w) * cout * cin * ks * ks, "flop"):
+    with _timed_conv(dims, cout, ks, pad, 1, y, False, f16=True):
         check(lib().wcmc_conv2d_out_f16(_ptr(x16), n, h, w, cin, _ptr(wp16), _ptr(bias), *_v(y), cout, ks, pad, _stream()), "conv2d_out_f16")
     return y
 
@@ -264,7 +258,7 @@ def conv2d_wgrad_x_raw(xs, xdims, dys, cout, ks, pad, weight_shape, want_bias=Tr
     elif _sw._PROFILER is None:
         check(lib().wcmc_conv2d_wgrad_bf16x3(*args, 0, cs, terms, _stream()), "conv2d_wgrad_bf16x3")
     else:       # bracket the split-K GEMM launch alone; the slab reduce + bias gradient is its own class
-        with _Timed(_wgrad_class(n, ho, cin, cout, ks), 2.0 * n * ho * wo * cout * cin * ks * ks, "flop"):
+        with _Timed(wgrad_launch_plan(n, h, w, cin, cout, ks, pad, terms)[0], 2.0 * n * ho * wo * cout * cin * ks * ks, "flop"):
             check(lib().wcmc_conv2d_wgrad_bf16x3(*args, 1, cs, terms, _stream()), "conv2d_wgrad_bf16x3")
         with _Timed("conv_wgrad_finish", 0.0, "flop"):
             check(lib().wcmc_conv2d_wgrad_bf16x3(*args, 2, cs, terms, _stream()), "conv2d_wgrad_bf16x3")
