@@ -704,6 +704,24 @@ int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* or
 int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm, int H, int W, int S, float* out, float* ipt,
                       float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
 
+/* ---------------------------------------------------------------- the same for the sample-based models (SBMC / LBMC interfaces)
+ * assemble_sample_tiles (csrc/sbmc_data.hip): the sample-based batch without gt and without target_image, for B tiles of P x P
+ *   pixels at origins[b] = (row, column) in FRAME coordinates, -pad <= origin <= dim + pad - P (device int32 [B][2]; the caller
+ *   checks them on the host, the kernel clamps the mirrored index), out of sbmc_s (H, W, S, 27), sbmc_p (H, W, S, 66; may be null
+ *   without use_sbmc_buf) and llpm (H, W, S, 37) or null: radiance (B, S, 3, P, P), features (B, S, F, P, P) and, with llpm, paths
+ *   (B, S, 36, P, P), channel for channel as the sample-patch entry point above lays them out (F = 24 | 3, + 66, + 1).  Every buffer
+ *   is per sample, so a position outside the frame is a copy of its mirror image's record: bit for bit what preprocessing
+ *   numpy.pad(raw, pad, 'symmetric') and assembling sample patches at origins + pad give.  One launch; copies only.
+ *   S > 0, 0 <= pad < min(H, W), P > 2*pad, P <= min(H, W) + 2*pad.
+ * finish_sample_frame (csrc/frame_tiles.hip): finish_frame with the noisy input of the sample-based models,
+ *   ipt (H, W, 3) = (sum over the S samples, in sample order, of sbmc_s[..., 0:3]) / S   (datasets.py:1248)
+ *   has_hit, out and the two optional previews as finish_frame. */
+int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B, int H, int W,
+                               int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
+                               float* paths, void* stream);
+int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S, float* out,
+                             float* ipt, float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

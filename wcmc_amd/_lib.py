@@ -129,6 +129,8 @@ SIGNATURES = {
     "wcmc_stitch_tiles": (I, [P, L, L, L, L, I, I, P, P, I, I, I, P, I, I, I, P, P, P, P]),
     "wcmc_assemble_kpcn_tiles": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P]),
     "wcmc_finish_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
+    "wcmc_assemble_sample_tiles": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P]),
+    "wcmc_finish_sample_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// What the data-step translation units share (preprocess.hip, multi_spp.hip, sbmc_data.hip): the raw channel map, the layout of
+// What the data-step translation units share (preprocess.hip, multi_spp.hip, sbmc_data.hip, frame_tiles.hip): the raw channel map, the layout of
 // the 44-channel KPCN buffer, the per-sample values and per-pixel closing arithmetic of _preprocess_kpcn, the finish pass, and
 // the host launchers of the two patch-assembly kernels (each kernel lives in ONE unit; the other unit calls its launcher).
 #pragma once
@@ -116,6 +116,14 @@ __device__ __forceinline__ void pp_kpcn_finish(float* __restrict__ out, const fl
 static unsigned pp_grid(int64_t work) {
   const int64_t b = ceil_div64(work, 256);
   return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
+// The mirror map of the tiles of a frame of any size (frame_tiles.hip, sbmc_data.hip): source index of position i in [-n, 2n) of a
+// line of n entries: d c b a | a b c d | d c b a (one reflection; pad < n).  The clamp costs two instructions and keeps a table the
+// host check let through from reading outside the buffers.
+__device__ __forceinline__ int ft_mirror(int i, int n) {
+  const int m = i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
+  return min(max(m, 0), n - 1);
 }
 
 // Launchers of the patch-assembly kernels (preprocess.hip, sbmc_data.hip).  The per-sample buffers hold S_total samples per pixel,

@@ -11,13 +11,6 @@
 
 namespace wcmc {
 
-// source index of position i in [-n, 2n) of a line of n entries: d c b a | a b c d | d c b a (one reflection; pad < n).  The clamp
-// costs two instructions and keeps a table the host check let through from reading outside the buffers.
-__device__ __forceinline__ int ft_mirror(int i, int n) {
-  const int m = i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
-  return min(max(m, 0), n - 1);
-}
-
 struct TileOut {
   float *din, *sin, *dbuf, *sbuf, *alb, *paths;
 };
@@ -139,9 +132,52 @@ __global__ __launch_bounds__(256) void ft_finish_frame_kernel(const float* __res
   }
 }
 
+// The closing pass of the sample-based models.  One thread per pixel: the noisy input is the mean over the samples of the first
+// three channels of sbmc_s (max(total, 0); datasets.py:1248), summed in sample order; has_hit as above.
+__global__ __launch_bounds__(256) void ft_finish_sample_frame_kernel(const float* __restrict__ out_rad, const float* __restrict__ sbmc_s,
+                                                                     const float* __restrict__ llpm, int64_t npix, int S,
+                                                                     float* __restrict__ out, float* __restrict__ ipt,
+                                                                     float* __restrict__ has_hit, uint8_t* __restrict__ prev_out,
+                                                                     uint8_t* __restrict__ prev_ipt) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const float* r = sbmc_s + p * S * 27;
+    const float* l = llpm + p * S * 37 + 25;
+    float sum = 0.f, acc[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < S; ++s) {
+      sum += l[s * 37];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) acc[ch] += r[s * 27 + ch];
+    }
+    const bool hit = sum / (float)S != 0.f;
+    float in[3], res[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      in[ch] = acc[ch] / (float)S;
+      res[ch] = hit ? out_rad[ch * npix + p] : in[ch];
+      ipt[p * 3 + ch] = in[ch];
+      out[p * 3 + ch] = res[ch];
+    }
+    has_hit[p] = hit ? 1.f : 0.f;
+    if (prev_out) ft_preview(res, prev_out + p * 3);
+    if (prev_ipt) ft_preview(in, prev_ipt + p * 3);
+  }
+}
+
 }  // namespace wcmc
 
 using namespace wcmc;
+
+extern "C" int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S,
+                                        float* out, float* ipt, float* has_hit, unsigned char* preview_out,
+                                        unsigned char* preview_ipt, void* stream) {
+  WCMC_REQUIRE(out_rad && sbmc_s && llpm && out && ipt && has_hit, WCMC_ERR_BAD_ARG, "finish_sample_frame: null pointer");
+  WCMC_REQUIRE(H > 0 && W > 0 && S > 0, WCMC_ERR_BAD_ARG, "finish_sample_frame: H, W and S must be positive (got %d, %d, %d)", H, W,
+               S);
+  const int64_t npix = (int64_t)H * W;
+  hipLaunchKernelGGL(ft_finish_sample_frame_kernel, dim3(pp_grid(npix)), dim3(256), 0, (hipStream_t)stream, out_rad, sbmc_s, llpm, npix,
+                     S, out, ipt, has_hit, preview_out, preview_ipt);
+  return check_launch("finish_sample_frame");
+}
 
 extern "C" int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P,
                                         int pad, float* diffuse_in, float* specular_in, float* diffuse_buffer,

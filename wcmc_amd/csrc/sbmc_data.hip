@@ -167,9 +167,91 @@ int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* ll
   return check_launch("assemble_sample_patches");
 }
 
+// ------------------------------------------------------------------ sample-based tiles of the mirror-extended frame (wcmc_amd.denoise)
+// sa_assemble_kernel with other addressing: the tile's origin is in frame coordinates and may lie up to `pad` pixels outside, the
+// source row is m(r) and each of the chunk's 32 pixels has its own source column m(c + px) (ft_mirror: a chunk that straddles a
+// frame edge runs backwards on the far side of it).  All three buffers are per sample, so a mirrored position is a copy of its
+// image's record -- nothing is recomputed -- and there is no gt source.  LDS tile and write pattern as above; the reads run along c
+// too, a pixel per half-wave.
+__global__ __launch_bounds__(256) void sa_assemble_tiles_kernel(SampleBatch a, const int* __restrict__ origins, int64_t units, int H,
+                                                                int W, int P) {
+  extern __shared__ __attribute__((aligned(16))) float sa_tile[];
+  const int nxc = (P + SA_XT - 1) / SA_XT;
+  const int64_t plane = (int64_t)P * P;
+  for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
+    int k = 2;
+    while (k > 0 && (a.src[k].nout == 0 || u < a.src[k].first)) --k;
+    const SampleSrc sr = a.src[k];
+    int64_t t = u - sr.first;
+    const int nsc = (sr.S + SA_SC - 1) / SA_SC;
+    const int sc = (int)(t % nsc); t /= nsc;
+    const int xc = (int)(t % nxc); t /= nxc;
+    const int y = (int)(t % P), b = (int)(t / P);
+    const int x0 = xc * SA_XT, xcnt = min(SA_XT, P - x0);
+    const int s0 = sc * SA_SC, scnt = min(SA_SC, sr.S - s0);
+    // (the host checks the origins; ft_mirror's clamp keeps a bad one from reading outside the buffers)
+    const int r = ft_mirror(origins[2 * b] + y, H), c = origins[2 * b + 1] + x0;
+    const int run = scnt * sr.C, LD = (SA_SC * sr.C) | 1;
+    const int64_t pitch = (int64_t)sr.Sp * sr.C;
+    const float* base = sr.p + (int64_t)r * W * pitch + (int64_t)s0 * sr.C;
+    // eight pixels at a time, 32 lanes along each pixel's run (128-byte segments): the source column is mirrored once per pixel,
+    // not once per float, and no index is divided
+    for (int px = threadIdx.x >> 5; px < xcnt; px += 8) {
+      const float* src = base + ft_mirror(c + px, W) * pitch;
+      float* dst = sa_tile + px * LD;
+#pragma unroll 4
+      for (int e = threadIdx.x & 31; e < run; e += 32) dst[e] = src[e];
+    }
+    __syncthreads();
+    const int rows = scnt * sr.nout;
+    for (int o = threadIdx.x; o < rows * SA_XT; o += 256) {
+      const int x = o & (SA_XT - 1), row = o / SA_XT;
+      if (x < xcnt) {
+        const int sl = row / sr.nout, ch = row - sl * sr.nout;
+        sa_dst(a, k, b, s0 + sl, sr.S, ch, plane)[(int64_t)y * P + x0 + x] = sa_tile[x * LD + sl * sr.C + ch];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace wcmc
 
 using namespace wcmc;
+
+extern "C" int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
+                                          int H, int W, int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance,
+                                          float* features, float* paths, void* stream) {
+  WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: null pointer");
+  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: use_sbmc_buf needs sbmc_p");
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: llpm needs a paths output");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: B, H, W, P must be positive and pad non-negative");
+  WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: S must be positive (got %d)", S);
+  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
+  SampleBatch a;
+  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = nullptr;
+  a.ng = use_g_buf ? 24 : 3;
+  a.F = a.ng + (use_sbmc_buf ? SA_CP : 0) + (llpm ? 1 : 0);
+  a.src[0] = SampleSrc{sbmc_s, SB_S, S, S, 3 + a.ng, 0};
+  a.src[1] = SampleSrc{sbmc_p, SA_CP, S, S, use_sbmc_buf ? SA_CP : 0, 0};
+  a.src[2] = SampleSrc{llpm, SA_CL, S, S, llpm ? SA_CL : 0, 0};
+  a.src[3] = SampleSrc{nullptr, SA_CG, 1, 1, 0, 0};
+  const int64_t rows = (int64_t)B * P * ((P + SA_XT - 1) / SA_XT);
+  int64_t units = 0;
+  for (int k = 0; k < 3; ++k) {
+    a.src[k].first = units;
+    if (a.src[k].nout > 0) units += rows * ((S + SA_SC - 1) / SA_SC);
+  }
+  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
+  hipLaunchKernelGGL(sa_assemble_tiles_kernel, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, (hipStream_t)stream,
+                     a, origins, units, H, W, P);
+  return check_launch("assemble_sample_tiles");
+}
 
 extern "C" int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples, int C, int max_depth, float* out_s, float* out_p,
                                     int tiled, void* stream) {

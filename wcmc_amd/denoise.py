@@ -1,7 +1,8 @@
-"""Denoise raw renders of any size with a trained KPCN model: no ground truth, no offline files, every pixel.
+"""Denoise raw renders of any size with a trained KPCN, SBMC or LBMC model: no ground truth, no offline files, every pixel.
 
     python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
         [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
+    python -m wcmc_amd.denoise ... --model_name SBMC_manifold --denoiser my_pkg.models:make_multisteps [--use_sbmc_buf] [--tile_pad N]
 
 Per input file (renderer output (H, W, S, 104), H and W at least 64): the first ``--spp`` samples (default: what the file holds; a
 file that holds fewer is continued by ``<stem>_1.npy``, ``<stem>_2.npy``, ... beside it) are streamed to the device in row bands,
@@ -10,8 +11,13 @@ memory, and the next file's bands cross while this one's network runs; ``--band_
 ``support.inference.denoise_frame`` runs the network over mirror-extended tiles and composites the result;
 ``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the result
 and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  The model flags are those of
-``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  Only the KPCN models are run here (SBMC / LBMC need the
-caller's base denoiser, as in ``wcmc_amd.evaluate``).  One line per frame reports the seconds of each phase.
+``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  One line per frame reports the seconds of each phase.
+
+A model whose name holds ``SBMC`` / ``LBMC`` is a ``train_sbmc`` / ``train_lbmc`` checkpoint around the caller's base denoiser
+(``--denoiser package.module:factory``, required; ``--disentangle``, ``--use_sbmc_buf``, ``--lr_dncnn`` as those launchers define them).
+Its frames are streamed as ``sbmc_s`` / ``sbmc_p`` / ``llpm`` and run through ``support.inference.denoise_sample_frame``; the P-buffer
+is one tensor.  ``--tile_pad N`` (default 32) is the overlap of the 128-pixel tiles: the denoiser's receptive field is the caller's,
+and an output that leaves fewer real pixels than the pad is refused.  For the KPCN models the pad is 32.
 """
 import os
 import struct
@@ -23,7 +29,7 @@ import torch
 
 from . import ops, train_kpcn
 from .support.datasets import MAX_CONTINUATIONS, dncnn_in_size
-from .support.inference import denoise_frame
+from .support.inference import denoise_frame, denoise_sample_frame, frame_tiles
 from .support.staging import FrameStreamer
 
 PATCH_SIZE, PAD_SIZE = 128, 32
@@ -134,26 +140,42 @@ def denoise_file(interface, fn, output_dir, args, device, frames=None):
     own = frames is None
     t0 = time.perf_counter()
     if own:
-        frames = FrameStreamer([fn], args.spp, device, band_rows=getattr(args, 'band_rows', None))
+        frames = make_streamer([fn], args, device)
     try:
-        kpcn, llpm = next(frames)
+        bufs = next(frames)
         ev0, ev1 = frames.finish_events
         ev1.synchronize()
     finally:
         if own:
             frames.close()
-    return denoise_buffers(interface, stem, kpcn, llpm, output_dir, args, time.perf_counter() - t0, ev0.elapsed_time(ev1) * 1e-3)
+    return _denoise_buffers(interface, stem, bufs, output_dir, args, time.perf_counter() - t0, ev0.elapsed_time(ev1) * 1e-3)
 
 
 def denoise_buffers(interface, stem, kpcn, llpm, output_dir, args, upload=0.0, preprocess=0.0):
     """Denoise the frame from its device buffers ``kpcn`` (H, W, 44) and ``llpm`` (H, W, S, 37), ready on the current stream, and write
     the outputs of ``stem``; returns the dict of phase seconds, with ``upload`` and ``preprocess`` as the caller measured them."""
+    return _denoise_buffers(interface, stem, (kpcn, llpm), output_dir, args, upload, preprocess)
+
+
+def denoise_sample_buffers(interface, stem, sbmc_s, sbmc_p, llpm, output_dir, args, upload=0.0, preprocess=0.0):
+    """``denoise_buffers`` for an SBMC / LBMC model, from ``sbmc_s`` (H, W, S, 27), ``sbmc_p`` (H, W, S, 66) or None, and ``llpm``."""
+    return _denoise_buffers(interface, stem, (sbmc_s, sbmc_p, llpm), output_dir, args, upload, preprocess)
+
+
+def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, preprocess=0.0):
+    """``bufs``: what the family's ``FrameStreamer`` yields, two buffers for a KPCN model and three for a sample-based one."""
     t1 = time.perf_counter()
+    llpm = bufs[-1]
     h, w, spp = llpm.shape[:3]
     batch_size = tile_batch_size(spp, args.tile_batch)
     times = {}
-    res = denoise_frame(interface, kpcn, llpm, args.use_llpm_buf, batch_size, want_pbuffers=args.save_pbuffer,
-                        patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
+    if len(bufs) == 3:
+        res = denoise_sample_frame(interface, bufs[0], bufs[1], llpm, args.use_llpm_buf, args.use_g_buf, args.use_sbmc_buf,
+                                   batch_size, want_pbuffers=args.save_pbuffer, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
+                                   preview=args.png, times=times)
+    else:
+        res = denoise_frame(interface, bufs[0], llpm, args.use_llpm_buf, batch_size, want_pbuffers=args.save_pbuffer,
+                            patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
     out, out_path = res[0], (res[3] if args.save_pbuffer else None)
     os.makedirs(output_dir, exist_ok=True)
     img = out.cpu().numpy()
@@ -179,11 +201,45 @@ def _model_path(args):
     return os.path.join(args.save, name)
 
 
+def sample_launcher(model_name):
+    """The launcher module whose ``init_model`` builds a model of this name, as test_models.py:166-171 dispatches: ``train_sbmc`` for
+    'SBMC', ``train_lbmc`` for 'LBMC', None for the KPCN route."""
+    if 'SBMC' in model_name:
+        from . import train_sbmc
+        return train_sbmc
+    if 'LBMC' in model_name:
+        from . import train_lbmc
+        return train_lbmc
+    return None
+
+
+def load_sample_interface(args, device):
+    """The trained SBMC / LBMC model through its launcher's ``init_model`` around ``--denoiser`` (``start_epoch`` forced nonzero: it
+    then restores the checkpoint).  The sizes are those of the 'sbmc' dataset at ``pnet_out_size`` 0 (test_models.py:42-45)."""
+    if not os.path.isfile(_model_path(args)):
+        raise FileNotFoundError(_model_path(args))
+    if args.start_epoch == 0:
+        args.start_epoch = 1
+    args.model_name = args.model_name[:-4] if args.model_name.endswith('.pth') else args.model_name
+    sizes = {'dncnn_in_size': dncnn_in_size('sbmc', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf, 0),
+             'pnet_in_size': 36 if args.use_llpm_buf else 0, 'pnet_out_size': 0}
+    interfaces, _ = sample_launcher(args.model_name).init_model(sizes, args, device)
+    return interfaces[0]
+
+
+def make_streamer(files, args, device):
+    """The ``FrameStreamer`` of the model's family over ``files``."""
+    kw = dict(base_model='sbmc', use_sbmc_buf=args.use_sbmc_buf) if sample_launcher(args.model_name) else {}
+    return FrameStreamer(files, args.spp, device, band_rows=getattr(args, 'band_rows', None), **kw)
+
+
 def load_interface(args, device):
-    """The trained model through ``train_kpcn.init_model`` (``start_epoch`` forced nonzero: it then restores the checkpoint)."""
+    """The trained model through ``train_kpcn.init_model`` (``start_epoch`` forced nonzero: it then restores the checkpoint), or, for
+    an SBMC / LBMC name, ``load_sample_interface``."""
+    if sample_launcher(args.model_name) is not None:
+        return load_sample_interface(args, device)
     if 'KPCN' not in args.model_name:
-        raise NotImplementedError("denoise: only KPCN models are run; an SBMC / LBMC model needs a base denoiser that the caller must "
-                                  "supply")
+        raise NotImplementedError("denoise: '%s' names neither a KPCN nor an SBMC / LBMC model" % args.model_name)
     if args.kpcn_ref:
         raise NotImplementedError("denoise: KPCN-Ref feeds the clean targets to the network; it cannot denoise a render without "
                                   "ground truth")
@@ -200,7 +256,7 @@ def load_interface(args, device):
 
 def build_parser():
     p = train_kpcn.build_parser()
-    p.description = "Denoise raw renders of any size with a trained KPCN model (no ground truth needed)."
+    p.description = "Denoise raw renders of any size with a trained KPCN, SBMC or LBMC model (no ground truth needed)."
     p.epilog = None
     for a in p._actions:
         if a.dest == 'desc':
@@ -217,11 +273,33 @@ def build_parser():
                         'bands are pinned on the host, one lies on the device, and the result does not depend on it')
     p.add_argument('--png', action='store_true', help='also write 8-bit tone-mapped <stem>_denoised.png and <stem>_input.png')
     p.add_argument('--save_pbuffer', action='store_true', help='also write the stitched P-buffer <stem>_pbuffer.npy (H, W, S, C)')
+    add_sample_arguments(p)
+    p.add_argument('--tile_pad', type=int, default=PAD_SIZE, metavar='N',
+                   help='overlap of the 128-pixel tiles on each side (SBMC / LBMC: at least what the denoiser\'s receptive field '
+                        'takes off a side of a tile; KPCN models: 32)')
+    return p
+
+
+def add_sample_arguments(p):
+    """What ``train_sbmc.add_common_arguments`` defines and ``train_kpcn.build_parser`` lacks (``--disentangle`` and ``--lr_dncnn`` are
+    there already, defined alike): the flags a sample-based model is built from."""
+    p.add_argument('--denoiser', type=str, default=None, metavar='package.module:factory',
+                   help='SBMC / LBMC: the base denoiser, factory(n_in) -> nn.Module mapping the batch dictionary to (B, 3, h, w).  '
+                        'Required for these models')
+    p.add_argument('--use_sbmc_buf', action='store_true', help='SBMC: use the sbmc-specific buffer.')
+    p.add_argument('--use_g_buf', action='store_false', help='SBMC / LBMC: leave the g-buffer out (as in train_sbmc).')
     return p
 
 
 def check_inputs(args):
     """Everything that can be refused before the GPU is touched: sample counts, continuation files, the tile batch size, the band."""
+    if sample_launcher(args.model_name) is not None:
+        from .train_sbmc import load_denoiser_factory
+        load_denoiser_factory(getattr(args, 'denoiser', None))        # (a DenoiserFactoryError, before any file is looked for)
+        frame_tiles(2 * PATCH_SIZE, 2 * PATCH_SIZE, PATCH_SIZE, args.tile_pad)          # (a pad without an interior)
+    elif getattr(args, 'tile_pad', PAD_SIZE) != PAD_SIZE:
+        raise ValueError("--tile_pad %d: the KPCN models are run with a pad of %d, the one their receptive field was checked "
+                         "against (DESIGN.md section 15)" % (args.tile_pad, PAD_SIZE))
     if getattr(args, 'band_rows', None) is not None and args.band_rows < 1:
         raise ValueError("--band_rows should be at least 1, got %d" % args.band_rows)
     for fn in args.input:
@@ -237,7 +315,7 @@ def main(argv=None):
     device = torch.device('cuda', args.device_id)
     torch.cuda.set_device(device)
     interface = load_interface(args, device)
-    frames = FrameStreamer(args.input, args.spp, device, band_rows=args.band_rows)
+    frames = make_streamer(args.input, args, device)
     try:
         return [denoise_file(interface, fn, args.output_dir, args, device, frames=frames) for fn in args.input]
     finally:

@@ -1,4 +1,4 @@
-"""Evaluate a trained KPCN model on full scenes: the counterpart of the reference's ``test_models.denoise``
+"""Evaluate a trained KPCN, SBMC or LBMC model on full scenes: the counterpart of the reference's ``test_models.denoise``
 (``test_models.py:104-277``).
 
 For every scene x spp: ``support.datasets.FullImageDataset`` (tiles assembled on the GPU from the offline-preprocessed files),
@@ -12,11 +12,12 @@ DSSIM, L1, MSE) under 4 tone maps (linear, _tonemap, tonemap, tonemap28) for the
         --output_dir OUT --scenes bathroom car --spps 8 32 [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
 
 The model flags are those of ``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth`` (a ``train_kpcn``
-checkpoint) loaded through ``train_kpcn.init_model``.  Only the KPCN models are evaluated here (SBMC / LBMC: their base
-denoisers are stand-ins in this build); the reference's quantize / TensorRT branches and its commented-out PFM output are
-not carried over.
+checkpoint) loaded through ``train_kpcn.init_model``.  A model whose name holds ``SBMC`` / ``LBMC`` is a ``train_sbmc`` /
+``train_lbmc`` checkpoint around the caller's base denoiser (``--denoiser package.module:factory``, required; ``--use_sbmc_buf``,
+``--disentangle`` as those launchers define them): its tiles come from ``support.datasets.SampleFullImageDataset`` (the offline
+``_sbmc_s`` / ``_sbmc_p`` files), its interface from that launcher's ``init_model``, and everything after the network is the same.
+The reference's quantize / TensorRT branches and its commented-out PFM output are not carried over.
 """
-import argparse
 import os
 
 import numpy as np
@@ -24,7 +25,8 @@ import torch
 
 from . import train_kpcn
 from .support import metrics as M
-from .support.datasets import FullImageDataset
+from .denoise import add_sample_arguments, load_sample_interface, sample_launcher
+from .support.datasets import FullImageDataset, SampleFullImageDataset
 from .support.inference import stitched_inference
 
 VALID_SIZE = 72                     # test_models.py:217-218
@@ -32,12 +34,12 @@ PATCH_SIZE = 128
 
 
 def load_input(filename, spp, args, device=None):
-    """test_models.py:37-46 for the KPCN models."""
+    """test_models.py:37-46."""
     if 'KPCN' in args.model_name:
         return FullImageDataset(filename, spp, 'kpcn', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf,
                                 args.pnet_out_size[0], device=device)
-    raise NotImplementedError("evaluate: only KPCN models are evaluated; an SBMC / LBMC model needs a base denoiser that the caller must supply "
-                              "(support.datasets.SampleFullImageDataset yields its tiles)")
+    assert 'BMC' in args.model_name, args.model_name
+    return SampleFullImageDataset(filename, spp, 'sbmc', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf, 0, device=device)
 
 
 def _model_path(args):
@@ -53,8 +55,9 @@ def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,
     assert os.path.isdir(input_dir), input_dir
     assert 'KPCN' in args.model_name or 'BMC' in args.model_name, args.model_name
     if 'KPCN' not in args.model_name:
-        raise NotImplementedError("evaluate: only KPCN models are evaluated; an SBMC / LBMC model needs a base denoiser that the caller must supply "
-                              "(support.datasets.SampleFullImageDataset yields its tiles)")
+        assert sample_launcher(args.model_name) is not None, args.model_name
+        from .train_sbmc import load_denoiser_factory
+        load_denoiser_factory(getattr(args, 'denoiser', None))        # (a DenoiserFactoryError, before any file is looked for)
     device = torch.device(device if device is not None else torch.cuda.current_device())
     spps = list(spps)
     if scenes is None:
@@ -84,6 +87,8 @@ def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,
         for j, spp in enumerate(spps):
             print("Samples per pixel:", spp)
             dataset = load_input(os.path.join(input_dir, scene + ".npy"), spp, args, device)
+            if interfaces is None and 'KPCN' not in args.model_name:
+                interfaces = [load_sample_interface(args, device)]    # test_models.py:166-169
             if interfaces is None:
                 # train_kpcn.init_model restores <save>/<model_name>.pth when start_epoch != 0 (test_models.py:163-171)
                 if args.start_epoch == 0:
@@ -144,7 +149,7 @@ def _save_figures(d, spp, model_name, out, ipt, tgt):
 
 def build_parser():
     p = train_kpcn.build_parser()
-    p.description = "Evaluate a trained KPCN model on full scenes (test_models.denoise)."
+    p.description = "Evaluate a trained KPCN, SBMC or LBMC model on full scenes (test_models.denoise)."
     for a in p._actions:
         if a.dest == 'desc':
             a.required = False                     # a training-run label; not needed to evaluate
@@ -153,10 +158,8 @@ def build_parser():
     p.add_argument('--scenes', type=str, nargs='*', default=None, help='scene names (default: every .npy under gt/)')
     p.add_argument('--spps', type=int, nargs='+', default=[8])
     p.add_argument('--save_figures', action='store_true', help='write the four PNGs per scene and spp (needs matplotlib)')
-    p.add_argument('--rhf', action='store_true', help="save the diffuse P-buffer of the first scene as .npy and stop")
-    p.add_argument('--use_g_buf', action='store_true', default=True, help=argparse.SUPPRESS)
-    p.add_argument('--use_sbmc_buf', action='store_true', default=False, help=argparse.SUPPRESS)
-    return p
+    p.add_argument('--rhf', action='store_true', help="save the P-buffer of the first scene (KPCN: the diffuse one) as .npy and stop")
+    return add_sample_arguments(p)
 
 
 def main(argv=None):

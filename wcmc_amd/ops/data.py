@@ -161,14 +161,24 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
     return out
 
 
-def preprocess_sbmc(sample, max_depth=5, tiled=None):
+def preprocess_sbmc(sample, max_depth=5, tiled=None, out_s=None, out_p=None):
     """``DenoiseDataset._preprocess_sbmc`` (datasets.py:363-485): sanitised raw (h,w,s,C) -> (sbmc_s (h,w,s,27), sbmc_p (h,w,s,66)).
     ``tiled``: None lets the library pick the form, False / True force the one-thread-per-element / the LDS-staged form (which
-    refuses records that are not 16-byte aligned); the two are bit-identical."""
+    refuses records that are not 16-byte aligned); the two are bit-identical.  ``out_s`` / ``out_p``: contiguous tensors of those
+    shapes to write into -- row slices of a frame's buffers when ``sample`` is a band of its rows (the function is per sample)."""
     _need_dense(sample, 4)
     h, w, s, c = sample.shape
-    out_s = torch.empty((h, w, s, 27), device=sample.device, dtype=torch.float32)
-    out_p = torch.empty((h, w, s, 11 * (max_depth + 1)), device=sample.device, dtype=torch.float32)
+    pc = 11 * (max_depth + 1)
+    for name, t, oc in (("out_s", out_s, 27), ("out_p", out_p, pc)):
+        if t is not None:
+            _need_dense(t, 4)
+            if tuple(t.shape) != (h, w, s, oc) or t.device != sample.device:
+                raise ValueError("preprocess_sbmc: %s should be (%d, %d, %d, %d) on %s, got %s on %s"
+                                 % (name, h, w, s, oc, sample.device, tuple(t.shape), t.device))
+    if out_s is None:
+        out_s = torch.empty((h, w, s, 27), device=sample.device, dtype=torch.float32)
+    if out_p is None:
+        out_p = torch.empty((h, w, s, pc), device=sample.device, dtype=torch.float32)
     check(lib().wcmc_preprocess_sbmc(_ptr(sample), h * w * s, c, max_depth, _ptr(out_s), _ptr(out_p),
                                      -1 if tiled is None else int(bool(tiled)), _stream()), "preprocess_sbmc")
     return out_s, out_p
@@ -445,4 +455,69 @@ def finish_frame(out_rad, kpcn, llpm, preview=False):
     pv = [torch.empty((h, w, 3), device=dev, dtype=torch.uint8) for _ in range(2)] if preview else [None, None]
     check(lib().wcmc_finish_frame(_ptr(out_rad), _ptr(kpcn), _ptr(llpm), h, w, llpm.shape[2], _ptr(out), _ptr(ipt), _ptr(has_hit),
                                   _ptr(pv[0]), _ptr(pv[1]), _stream()), "finish_frame")
+    return (out, ipt, has_hit, pv[0], pv[1]) if preview else (out, ipt, has_hit)
+
+
+# ---------------------------------------------------------------------------------- ... with a sample-based model (csrc/sbmc_data.hip)
+def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_g_buf=True, use_sbmc_buf=True, check_origins=True):
+    """The inference batch of the SBMC / LBMC interfaces -- ``assemble_sample_patches`` without ``gt`` and without ``target_image`` --
+    for tiles of ``patch`` pixels at ``origins`` ((B, 2) int32 device tensor of (row, column) in frame coordinates, from ``-pad``
+    upward) of the frame extended by ``pad`` pixels by mirror reflection with the edge repeated (``wcmc_assemble_sample_tiles``; bit
+    for bit the ``radiance`` / ``features`` / ``paths`` of the ``np.pad(raw, pad, 'symmetric')`` frame at ``origins + pad``, which is
+    never built).  ``sbmc_p`` may be None without ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  The
+    origins are data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the
+    table once (checking a device tensor here synchronises)."""
+    _need_cuda(sbmc_s)
+    if not origins.is_cuda:
+        raise RuntimeError("assemble_sample_tiles: origins must be a device tensor")
+    if sbmc_s.dim() != 4 or sbmc_s.shape[3] != 27 or sbmc_s.shape[2] < 1 or not sbmc_s.is_contiguous():
+        raise ValueError("assemble_sample_tiles: sbmc_s should be contiguous (H, W, S, 27), got %s" % (tuple(sbmc_s.shape),))
+    h, w, s = sbmc_s.shape[:3]
+    for name, t, c in (("sbmc_p", sbmc_p if use_sbmc_buf else None, 66), ("llpm", llpm, 37)):
+        if t is not None and (tuple(t.shape) != (h, w, s, c) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError("assemble_sample_tiles: %s should be a contiguous fp32 (%d, %d, %d, %d) device tensor, got %s"
+                             % (name, h, w, s, c, tuple(t.shape)))
+    if use_sbmc_buf and sbmc_p is None:
+        raise ValueError("assemble_sample_tiles: use_sbmc_buf needs sbmc_p")
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
+    if check_origins:
+        check_tile_origins(origins, h, w, patch, pad, who="assemble_sample_tiles")
+    b = origins.shape[0]
+    f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
+    shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
+    if llpm is not None:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    # ONE allocation, the entries are 256-byte aligned views of it (as assemble_kpcn_tiles)
+    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
+    flat = torch.empty(sum(sizes.values()), device=sbmc_s.device, dtype=torch.float32)
+    out, off = {}, 0
+    for k, shp in shapes.items():
+        out[k] = flat[off:off + math.prod(shp)].view(shp)
+        off += sizes[k]
+    check(lib().wcmc_assemble_sample_tiles(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
+                                           ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, int(bool(use_g_buf)),
+                                           int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
+                                           _ptr(out.get("paths")), _stream()), "assemble_sample_tiles")
+    return out
+
+
+def finish_sample_frame(out_rad, sbmc_s, llpm, preview=False):
+    """``finish_frame`` for the sample-based models (``wcmc_finish_sample_frame``): out_rad (3, H, W) stitched radiance, sbmc_s
+    (H, W, S, 27), llpm (H, W, S, 37) -> ``(out, ipt, has_hit)`` with the noisy input ``ipt`` (H, W, 3) the mean over the samples of
+    ``sbmc_s[..., 0:3]`` (datasets.py:1248; summed in sample order), ``has_hit`` and the composite as ``finish_frame``'s;
+    ``preview=True`` adds the two (H, W, 3) uint8 previews."""
+    _need_cuda(out_rad, sbmc_s, llpm)
+    h, w = sbmc_s.shape[:2]
+    if (tuple(out_rad.shape) != (3, h, w) or sbmc_s.dim() != 4 or sbmc_s.shape[3] != 27 or sbmc_s.shape[2] < 1
+            or tuple(llpm.shape) != (h, w, sbmc_s.shape[2], 37)
+            or not (out_rad.is_contiguous() and sbmc_s.is_contiguous() and llpm.is_contiguous())):
+        raise ValueError("finish_sample_frame: out_rad should be contiguous (3, H, W), sbmc_s (H, W, S, 27) and llpm (H, W, S, 37), "
+                         "got %s, %s, %s" % (tuple(out_rad.shape), tuple(sbmc_s.shape), tuple(llpm.shape)))
+    dev = sbmc_s.device
+    out = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
+    ipt = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
+    has_hit = torch.empty((h, w), device=dev, dtype=torch.float32)
+    pv = [torch.empty((h, w, 3), device=dev, dtype=torch.uint8) for _ in range(2)] if preview else [None, None]
+    check(lib().wcmc_finish_sample_frame(_ptr(out_rad), _ptr(sbmc_s), _ptr(llpm), h, w, sbmc_s.shape[2], _ptr(out), _ptr(ipt),
+                                         _ptr(has_hit), _ptr(pv[0]), _ptr(pv[1]), _stream()), "finish_sample_frame")
     return (out, ipt, has_hit, pv[0], pv[1]) if preview else (out, ipt, has_hit)

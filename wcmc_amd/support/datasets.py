@@ -260,7 +260,7 @@ class FullImageDataset:
 class SampleFullImageDataset(FullImageDataset):
     """``FullImageDataset`` for ``base_model`` 'sbmc' / 'lbmc' (``datasets.py:1193-1196, 1323-1351, 1364-1416``): the files of
     ``_load_full_buffer`` with ``has_hit``, tiles of the sample-based dictionary.  A class of its own because ``FullImageDataset``
-    keeps refusing these models, as ``evaluate.py`` does: nothing in this package can denoise their tiles."""
+    keeps refusing these models; ``evaluate.py`` picks this one for an SBMC / LBMC model name."""
     SAMPLE_BASED = True
 
 

@@ -185,3 +185,61 @@ def denoise_frame(interface, kpcn, llpm, use_llpm_buf=True, batch_size=8, want_p
             torch.cuda.synchronize(kpcn.device)
             times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=len(coords))
     return res[:3] + ((out_path,) if want_pbuffers else ()) + (tuple(res[3:]) if preview else ())
+
+
+def check_output_size(ho, wo, patch_size, pad_size):
+    """A network output of ``ho x wo`` pixels is padded back to the tile by replication, ``(patch - ho + 1) // 2`` pixels at the most
+    on a side (``ops.stitch_tiles``); those pixels must stay outside the owned window ``[pad, patch - pad)``.  The KPCN models'
+    receptive field is known; a caller's denoiser is checked here."""
+    if (patch_size - ho + 1) // 2 > pad_size or (patch_size - wo + 1) // 2 > pad_size:
+        raise ValueError("denoise_sample_frame: the denoiser turns a %d-pixel tile into a %d x %d output, so up to %d pixels of a "
+                         "side are replicated, more than the %d of --tile_pad: the owned window of a tile would hold padding"
+                         % (patch_size, ho, wo, max((patch_size - ho + 1) // 2, (patch_size - wo + 1) // 2), pad_size))
+
+
+def denoise_sample_frame(interface, sbmc_s, sbmc_p, llpm, use_llpm_buf=True, use_g_buf=True, use_sbmc_buf=True, batch_size=8,
+                         want_pbuffers=False, patch_size=128, pad_size=32, preview=False, times=None):
+    """``denoise_frame`` for the sample-based interfaces (``SBMCInterface`` / ``LBMCInterface`` around the caller's denoiser), from
+    the device buffers ``sbmc_s`` (H, W, S, 27), ``sbmc_p`` (H, W, S, 66; None without ``use_sbmc_buf``) and ``llpm`` (H, W, S, 37):
+    per batch of ``frame_tiles`` one ``ops.assemble_sample_tiles`` launch, ``interface.denoise_batch`` and one ``ops.stitch_tiles``
+    launch; then ``ops.finish_sample_frame``.  ``llpm`` is always needed (``has_hit``); it feeds the network with ``use_llpm_buf``.
+    The denoiser's receptive field is the caller's: an output so small that replicated pixels would reach an owned window is a
+    ``ValueError`` after the first batch (``check_output_size``).  Returns what ``denoise_frame`` returns; the P-buffer is one
+    (S, C, H, W) tensor."""
+    import time
+    from .. import ops
+    h, w = sbmc_s.shape[:2]
+    coords = frame_tiles(h, w, patch_size, pad_size)
+    ops.check_tile_coords(coords, h, w, patch_size)
+    ops.check_tile_origins([c[4:6] for c in coords], h, w, patch_size, pad_size, who="denoise_sample_frame")
+    interface.to_eval_mode()
+    if times is not None:
+        torch.cuda.synchronize(sbmc_s.device)
+        t0 = time.perf_counter()
+    with torch.no_grad():
+        coords_dev = torch.tensor(coords, dtype=torch.int32, device=sbmc_s.device)
+        origins_dev = coords_dev[:, 4:6].contiguous()
+        out_rad = torch.zeros((3, h, w), device=sbmc_s.device)
+        out_path = None
+        for k in range(0, len(coords), batch_size):
+            batch = ops.assemble_sample_tiles(sbmc_s, sbmc_p if use_sbmc_buf else None, llpm if use_llpm_buf else None,
+                                              origins_dev[k:k + batch_size], patch_size, pad_size, use_g_buf, use_sbmc_buf,
+                                              check_origins=False)
+            out, p_buffer = interface.denoise_batch(batch)
+            if k == 0:
+                check_output_size(out.shape[2], out.shape[3], patch_size, pad_size)
+            if not (want_pbuffers and p_buffer is not None):
+                p_buffer = None
+            else:
+                if out_path is None:
+                    out_path = torch.zeros((p_buffer.shape[1], p_buffer.shape[2], h, w), device=p_buffer.device)
+                p_buffer = p_buffer.contiguous()
+            ops.stitch_tiles(out, p_buffer, coords_dev[k:k + batch_size], out_rad, out_path, patch_size)
+        if times is not None:
+            torch.cuda.synchronize(sbmc_s.device)
+            t1 = time.perf_counter()
+        res = ops.finish_sample_frame(out_rad, sbmc_s, llpm, preview=preview)
+        if times is not None:
+            torch.cuda.synchronize(sbmc_s.device)
+            times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=len(coords))
+    return res[:3] + ((out_path,) if want_pbuffers else ()) + (tuple(res[3:]) if preview else ())

@@ -685,8 +685,9 @@ class SBMCInterface(BaseInterface):
     @staticmethod
     def _assemble(batch, p_regress):
         """interfaces.py:390-403: features' = cat([features, P, P.var(1).mean(1) / S (detached, per sample)], 2)."""
-        return {'target_image': batch['target_image'], 'radiance': batch['radiance'],
-                'features': _ops.sample_features_cat(batch['features'], p_regress)}
+        out = {'target_image': batch['target_image']} if 'target_image' in batch else {}       # (denoise_batch: no target)
+        out.update(radiance=batch['radiance'], features=_ops.sample_features_cat(batch['features'], p_regress))
+        return out
 
     def _dump_pbuffer(self, p_buffer):
         if not os.path.isdir('../LLPM_results'):     # interfaces.py:371-374 (debug PNG every 1000 iterations)
@@ -763,6 +764,16 @@ class SBMCInterface(BaseInterface):
         out = self._regress_forward(batch)
         self._score(self.loss_funcs['l_test'](out, crop_like(batch['target_image'], out)))
         return out, p_buffer
+
+    def denoise_batch(self, batch):
+        """``validate_batch`` for a batch without ``target_image`` (``ops.assemble_sample_tiles``): the same backbone, split,
+        assembly and ``dncnn``, nothing scored and ``m_losses`` untouched.  Returns ``(radiance, p_buffer)``."""
+        p_buffer = None
+        batch = {k: batch[k] for k in ('radiance', 'features') + (('paths',) if self.use_llpm_buf else ())}
+        if self.use_llpm_buf:
+            _, p_buffer = self._split(self._manifold_forward(batch), train=False)
+            batch = self._assemble(batch, p_buffer)
+        return self._regress_forward(batch), p_buffer
 
     def _score(self, L_total):
         if self.m_losses['m_val'] == 0.0 and self.m_losses['m_val'].device != L_total.device:

@@ -13,6 +13,9 @@ image maximum of the mean depth and the backward differences, and both of those 
     hands ``(kpcn, llpm)`` over behind an event, as ``loader.ImageStager`` hands its buffers over.  It runs one frame ahead of the
     consumer: frame n + 1 crosses PCIe while the network runs frame n and the host writes its files.
 
+For an SBMC / LBMC model (``base_model='sbmc' | 'lbmc'``) the same threads, stream and ring produce ``(sbmc_s, sbmc_p or None, llpm)``:
+every buffer is per sample, so a band is final when ``preprocess_sbmc`` and ``preprocess_llpm`` have run on it.
+
 ``loader.py`` stages whole images for training and stays as it is; its stop-flag queue idiom (``ImageStager._get`` / ``_put``) is
 reused here.  ``scripts/time_denoise_stream.py`` measures the route against ``denoise.upload_raw``.
 """
@@ -183,9 +186,12 @@ class _FrameStream:
     """The state and the two threads' code behind ``FrameStreamer``.  Neither the producer thread nor the consumer's generator holds
     the ``FrameStreamer`` itself, so dropping that one ends them."""
 
-    def __init__(self, files, spp, device, band_rows=None, workers=4, max_depth=5, target_bytes=BAND_TARGET_BYTES):
+    def __init__(self, files, spp, device, band_rows=None, workers=4, max_depth=5, target_bytes=BAND_TARGET_BYTES,
+                 base_model='kpcn', use_sbmc_buf=True):
+        from .datasets import sample_flags
         if band_rows is not None and int(band_rows) < 1:
             raise ValueError("band_rows should be at least 1, got %d" % band_rows)
+        self.base_model, _, self.use_sbmc_buf = sample_flags(base_model, True, use_sbmc_buf)     # ('lbmc': 'sbmc' without sbmc_p)
         self.files, self.spp = list(files), spp
         self.band_rows = None if band_rows is None else int(band_rows)
         self.workers, self.max_depth, self.target_bytes = max(1, int(workers)), max_depth, int(target_bytes)
@@ -195,13 +201,16 @@ class _FrameStream:
         self.copy_stream = copy_stream(self.device)
         self.ring, self.finish_events, self.bytes_moved = None, None, 0
         self._band = None                                             # the device band buffer (flat)
+        self._scratch_p = None                                        # sample-based without sbmc_p: one band's unread out_p (flat)
 
     def _frame(self, fn, ring, stop):
-        """Enqueue one frame on the copy stream; ``(kpcn, llpm, before_end, after_end)`` or None when the consumer has gone."""
+        """Enqueue one frame on the copy stream; ``(buffers, before_end, after_end)`` or None when the consumer has gone."""
         from .. import ops
         from ..denoise import read_raw
         parts, spp = read_raw(fn, self.spp)
         h, w = parts[0].shape[:2]
+        if self.base_model != 'kpcn':
+            return self._sample_frame(parts, spp, h, w, ring, stop)
         band_rows = min(h, self.band_rows or default_band_rows(h, w, spp, self.target_bytes))
         reader = BandReader(parts, band_rows, self.workers, ring=ring, stop=stop)
         bands, seen = iter(reader), 0
@@ -233,7 +242,52 @@ class _FrameStream:
                 ev1.record(self.copy_stream)
         finally:
             bands.close()
-        return kpcn, llpm, ev0, ev1
+        return (kpcn, llpm), ev0, ev1
+
+    def _sample_frame(self, parts, spp, h, w, ring, stop):
+        """``_frame`` for the sample-based models: ``((sbmc_s, sbmc_p or None, llpm), event, event)``.  Every buffer is per sample, so a
+        band is final when its kernels have run: no begin / end, no workspace.  ``wcmc_preprocess_sbmc`` writes both of its outputs;
+        without ``use_sbmc_buf`` the second goes to a band-sized scratch that the next band overwrites."""
+        from .. import ops
+        band_rows = min(h, self.band_rows or default_band_rows(h, w, spp, self.target_bytes))
+        reader = BandReader(parts, band_rows, self.workers, ring=ring, stop=stop)
+        bands, seen = iter(reader), 0
+        pc = 11 * (self.max_depth + 1)
+        try:
+            with torch.cuda.stream(self.copy_stream):
+                new = lambda c: torch.empty((h, w, spp, c), device=self.device, dtype=torch.float32)   # noqa: E731
+                sbmc_s, llpm = new(27), new(7 + 5 * (self.max_depth + 1))
+                sbmc_p = new(pc) if self.use_sbmc_buf else None
+                n = band_rows * w * spp * RAW_C
+                if self._band is None or self._band.numel() < n:
+                    self._band = None
+                    self._band = torch.empty(n, device=self.device, dtype=torch.float32)
+                n = 0 if self.use_sbmc_buf else band_rows * w * spp * pc
+                if self._scratch_p is None or self._scratch_p.numel() < n:
+                    self._scratch_p = None
+                    self._scratch_p = torch.empty(n, device=self.device, dtype=torch.float32)
+                for slot, row0, rows in bands:
+                    shape = (rows, w, spp, RAW_C)
+                    d_band = self._band[:math.prod(shape)].view(shape)
+                    d_band.copy_(ring.view(slot, shape), non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(self.copy_stream)
+                    ring.release(slot, ev)                            # (the event guards the pinned slot's reuse)
+                    ops.sanitize_(d_band)
+                    out_p = (sbmc_p[row0:row0 + rows] if self.use_sbmc_buf
+                             else self._scratch_p[:rows * w * spp * pc].view(rows, w, spp, pc))
+                    ops.preprocess_sbmc(d_band, self.max_depth, out_s=sbmc_s[row0:row0 + rows], out_p=out_p)
+                    ops.preprocess_llpm(d_band, self.max_depth, out=llpm[row0:row0 + rows])
+                    self.bytes_moved += d_band.numel() * 4
+                    seen += 1
+                if seen < len(reader.ranges):                         # the reader gave up: the stop flag is set
+                    return None
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record(self.copy_stream)                          # (no finish pass: the pair brackets nothing)
+                ev1.record(self.copy_stream)
+        finally:
+            bands.close()
+        return (sbmc_s, sbmc_p, llpm), ev0, ev1
 
     def _produce(self, out_q, permits, stop):
         try:
@@ -251,7 +305,7 @@ class _FrameStream:
         except BaseException as exc:                                  # surface reader / device errors in the consumer
             ImageStager._put(out_q, exc, stop)
         finally:
-            self._band = None
+            self._band = self._scratch_p = None
 
     def _consume(self):
         out_q, stop, permits = queue.Queue(maxsize=1), threading.Event(), threading.Semaphore(2)
@@ -268,15 +322,16 @@ class _FrameStream:
                         raise exc
                     finally:
                         del exc
-                kpcn, llpm, ev0, ev1 = got
+                bufs, ev0, ev1 = got
                 del got
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev1)                                   # the consumer's stream, not the host, waits
-                kpcn.record_stream(cur)
-                llpm.record_stream(cur)
+                for t in bufs:
+                    if t is not None:
+                        t.record_stream(cur)
                 self.finish_events = (ev0, ev1)
-                yield kpcn, llpm
-                del kpcn, llpm
+                yield bufs
+                del bufs, t
                 permits.release()
         finally:
             stop.set()                                                # the producer's and the readers' queue waits poll this flag
@@ -307,12 +362,18 @@ class FrameStreamer:
     besides: one band and the (H, W) workspace; pinned host memory: ``workers + 2`` bands.  ``band_rows=None`` takes
     ``default_band_rows`` of each frame; a number is a memory control, never another route.
 
+    ``base_model='sbmc'`` / ``'lbmc'``: the frames of the sample-based models, ``(sbmc_s (H, W, S, 27), sbmc_p (H, W, S, 66) or None,
+    llpm)`` -- each band through ``ops.sanitize_``, ``ops.preprocess_sbmc(out_s=rows, out_p=rows)`` and ``ops.preprocess_llpm(out=rows)``
+    on the same stream, pinned ring and one-frame-ahead rule; everything is per sample, so there is no workspace and no finish pass.
+    ``sbmc_p`` exists only for 'sbmc' with ``use_sbmc_buf`` (otherwise the kernel's second output goes to one band of scratch).
+
     ``finish_events``: the timing events around the last frame's ``preprocess_kpcn_end``; ``ring``: the pinned ring, once the first
     band has been read.  Reader and device errors are raised in the consumer; a consumer that leaves early (``break``, an exception,
     ``close()``) stops the threads and releases the ring."""
 
-    def __init__(self, files, spp, device, band_rows=None, workers=4, max_depth=5, target_bytes=BAND_TARGET_BYTES):
-        self._stream = _FrameStream(files, spp, device, band_rows, workers, max_depth, target_bytes)
+    def __init__(self, files, spp, device, band_rows=None, workers=4, max_depth=5, target_bytes=BAND_TARGET_BYTES,
+                 base_model='kpcn', use_sbmc_buf=True):
+        self._stream = _FrameStream(files, spp, device, band_rows, workers, max_depth, target_bytes, base_model, use_sbmc_buf)
         self._frames = None                                           # the consumer's generator, from the first next()
 
     finish_events = property(lambda self: self._stream.finish_events)
