@@ -163,13 +163,13 @@ def denoise_sample_buffers(interface, stem, sbmc_s, sbmc_p, llpm, output_dir, ar
 
 
 def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, preprocess=0.0):
-    """``bufs``: what the family's ``FrameStreamer`` yields, two buffers for a KPCN model and three for a sample-based one."""
+    """``bufs``: what ``make_streamer``'s ``FrameStreamer`` yields for the family that the model's name stands for."""
     t1 = time.perf_counter()
     llpm = bufs[-1]
     h, w, spp = llpm.shape[:3]
     batch_size = tile_batch_size(spp, args.tile_batch)
     times = {}
-    if len(bufs) == 3:
+    if sample_launcher(args.model_name) is not None:
         res = denoise_sample_frame(interface, bufs[0], bufs[1], llpm, args.use_llpm_buf, args.use_g_buf, args.use_sbmc_buf,
                                    batch_size, want_pbuffers=args.save_pbuffer, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
                                    preview=args.png, times=times)
@@ -213,18 +213,28 @@ def sample_launcher(model_name):
     return None
 
 
-def load_sample_interface(args, device):
-    """The trained SBMC / LBMC model through its launcher's ``init_model`` around ``--denoiser`` (``start_epoch`` forced nonzero: it
-    then restores the checkpoint).  The sizes are those of the 'sbmc' dataset at ``pnet_out_size`` 0 (test_models.py:42-45)."""
+def restore_interface(args, device):
+    """The trained model ``<save>/<model_name>.pth`` of any family, through ``init_model`` of the launcher that trained it
+    (``sample_launcher``, around ``--denoiser``; ``train_kpcn`` otherwise) with ``start_epoch`` forced nonzero: it then restores the
+    checkpoint.  The sizes are the evaluation datasets' (test_models.py:37-46): those of 'sbmc' at ``pnet_out_size`` 0 for a
+    sample-based model, those of 'kpcn' at ``--pnet_out_size`` otherwise.  Refuses nothing but a missing file."""
     if not os.path.isfile(_model_path(args)):
         raise FileNotFoundError(_model_path(args))
     if args.start_epoch == 0:
         args.start_epoch = 1
     args.model_name = args.model_name[:-4] if args.model_name.endswith('.pth') else args.model_name
-    sizes = {'dncnn_in_size': dncnn_in_size('sbmc', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf, 0),
-             'pnet_in_size': 36 if args.use_llpm_buf else 0, 'pnet_out_size': 0}
-    interfaces, _ = sample_launcher(args.model_name).init_model(sizes, args, device)
+    launcher = sample_launcher(args.model_name)
+    if launcher is not None:
+        pnet_out, n_in = 0, dncnn_in_size('sbmc', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf, 0)
+    else:
+        launcher, pnet_out = train_kpcn, args.pnet_out_size[0]
+        n_in = dncnn_in_size('kpcn', True, False, args.use_llpm_buf, pnet_out)
+    sizes = {'dncnn_in_size': n_in, 'pnet_in_size': 36 if args.use_llpm_buf else 0, 'pnet_out_size': pnet_out}
+    interfaces, _ = launcher.init_model(sizes, args, device)
     return interfaces[0]
+
+
+load_sample_interface = restore_interface               # (the name the sample-based route was given first)
 
 
 def make_streamer(files, args, device):
@@ -234,24 +244,14 @@ def make_streamer(files, args, device):
 
 
 def load_interface(args, device):
-    """The trained model through ``train_kpcn.init_model`` (``start_epoch`` forced nonzero: it then restores the checkpoint), or, for
-    an SBMC / LBMC name, ``load_sample_interface``."""
-    if sample_launcher(args.model_name) is not None:
-        return load_sample_interface(args, device)
-    if 'KPCN' not in args.model_name:
-        raise NotImplementedError("denoise: '%s' names neither a KPCN nor an SBMC / LBMC model" % args.model_name)
-    if args.kpcn_ref:
-        raise NotImplementedError("denoise: KPCN-Ref feeds the clean targets to the network; it cannot denoise a render without "
-                                  "ground truth")
-    if not os.path.isfile(_model_path(args)):
-        raise FileNotFoundError(_model_path(args))
-    if args.start_epoch == 0:
-        args.start_epoch = 1
-    args.model_name = args.model_name[:-4] if args.model_name.endswith('.pth') else args.model_name
-    sizes = {'dncnn_in_size': dncnn_in_size('kpcn', True, False, args.use_llpm_buf, args.pnet_out_size[0]),
-             'pnet_in_size': 36 if args.use_llpm_buf else 0, 'pnet_out_size': args.pnet_out_size[0]}
-    interfaces, _ = train_kpcn.init_model(sizes, args, device)
-    return interfaces[0]
+    """``restore_interface`` for a model that can denoise a render without ground truth: a KPCN (not KPCN-Ref), SBMC or LBMC one."""
+    if sample_launcher(args.model_name) is None:
+        if 'KPCN' not in args.model_name:
+            raise NotImplementedError("denoise: '%s' names neither a KPCN nor an SBMC / LBMC model" % args.model_name)
+        if args.kpcn_ref:
+            raise NotImplementedError("denoise: KPCN-Ref feeds the clean targets to the network; it cannot denoise a render without "
+                                      "ground truth")
+    return restore_interface(args, device)
 
 
 def build_parser():

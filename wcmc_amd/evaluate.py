@@ -25,7 +25,7 @@ import torch
 
 from . import train_kpcn
 from .support import metrics as M
-from .denoise import add_sample_arguments, load_sample_interface, sample_launcher
+from .denoise import _model_path, add_sample_arguments, restore_interface, sample_launcher
 from .support.datasets import FullImageDataset, SampleFullImageDataset
 from .support.inference import stitched_inference
 
@@ -40,11 +40,6 @@ def load_input(filename, spp, args, device=None):
                                 args.pnet_out_size[0], device=device)
     assert 'BMC' in args.model_name, args.model_name
     return SampleFullImageDataset(filename, spp, 'sbmc', args.use_g_buf, args.use_sbmc_buf, args.use_llpm_buf, 0, device=device)
-
-
-def _model_path(args):
-    name = args.model_name if args.model_name.endswith('.pth') else args.model_name + '.pth'
-    return os.path.join(args.save, name)
 
 
 def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,), save_figures=False, rhf=False,
@@ -78,7 +73,7 @@ def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,
             raise FileNotFoundError(filename)
 
     crop = (PATCH_SIZE - VALID_SIZE) // 2
-    interfaces = None
+    interface = None
     for i, scene in enumerate(scenes):
         if scene.endswith(".npy"):
             scene = scene[:-4]
@@ -87,17 +82,9 @@ def denoise(args, input_dir, output_dir="../test_suite_2", scenes=None, spps=(8,
         for j, spp in enumerate(spps):
             print("Samples per pixel:", spp)
             dataset = load_input(os.path.join(input_dir, scene + ".npy"), spp, args, device)
-            if interfaces is None and 'KPCN' not in args.model_name:
-                interfaces = [load_sample_interface(args, device)]    # test_models.py:166-169
-            if interfaces is None:
-                # train_kpcn.init_model restores <save>/<model_name>.pth when start_epoch != 0 (test_models.py:163-171)
-                if args.start_epoch == 0:
-                    args.start_epoch = 1
-                args.model_name = args.model_name[:-4] if args.model_name.endswith('.pth') else args.model_name
-                sizes = {'dncnn_in_size': dataset.dncnn_in_size, 'pnet_in_size': dataset.pnet_in_size,
-                         'pnet_out_size': dataset.pnet_out_size}
-                interfaces, _ = train_kpcn.init_model(sizes, args, device)
-            out_rad, out_path = stitched_inference(interfaces[0], dataset, PATCH_SIZE, args.use_llpm_buf)
+            if interface is None:                  # (after the first dataset has loaded; KPCN-Ref is evaluated too)
+                interface = restore_interface(args, device)           # test_models.py:163-171
+            out_rad, out_path = stitched_inference(interface, dataset, PATCH_SIZE, args.use_llpm_buf)
 
             if out_path is not None and rhf:
                 print('Saving P-buffer as numpy file for RHF-like visualization...')

@@ -117,16 +117,34 @@ def _check_prefix(who, spp, s_total):
     return int(spp)
 
 
+def _aligned_views(shapes, device):
+    """``{name: fp32 tensor of shape}`` for the ordered ``shapes``, every entry a view of ONE allocation and starting on a 256-byte
+    boundary of it: a consumer on another stream keeps the batch alive with one `record_stream` and frees one block (nine of each
+    cost the training thread 0.25 ms per step: scripts/diag_loader_gap.py)."""
+    counts = [math.prod(shp) for shp in shapes.values()]
+    flat = torch.empty(sum((n + 63) // 64 * 64 for n in counts), device=device, dtype=torch.float32)
+    out, off = {}, 0
+    for (k, shp), n in zip(shapes.items(), counts):
+        out[k] = flat[off:off + n].view(shp)
+        off += (n + 63) // 64 * 64
+    return out
+
+
+def _need_origins(who, origins):
+    """The (B, 2) window origins as the assembly kernels read them: a contiguous int32 device tensor."""
+    if not origins.is_cuda:
+        raise RuntimeError("%s: origins must be a device tensor" % who)
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
+
+
 def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
     """The batch dictionary of the KPCN base model for windows of `patch` pixels at `origins` ((B, 2) int32 device
     tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device).  ``spp``: the batch takes
     the first ``spp`` of llpm's samples (``wcmc_assemble_kpcn_patches_prefix``; ``kpcn`` is then that count's buffer); None: all."""
     _need_cuda(kpcn, gt)
-    if not origins.is_cuda:
-        raise RuntimeError("assemble_kpcn_patches: origins must be a device tensor")
+    _need_origins("assemble_kpcn_patches", origins)
     h, w = kpcn.shape[:2]
     assert kpcn.shape == (h, w, 44) and gt.shape == (h, w, 9) and kpcn.is_contiguous() and gt.is_contiguous()
-    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
     b, s = origins.shape[0], 0
     if llpm is not None:
         assert llpm.shape[:2] == (h, w) and llpm.shape[3] == 37 and llpm.is_contiguous()
@@ -134,7 +152,6 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
     s_total = s
     if spp is not None and llpm is not None:
         s = _check_prefix("assemble_kpcn_patches", spp, s_total)
-    dev = kpcn.device
     cin = 35 if llpm is not None else 34
     shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
               "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
@@ -142,14 +159,7 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
               "target_specular": (b, 3, patch, patch), "target_total": (b, 3, patch, patch)}
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
-    # ONE allocation, the entries are views of it: a consumer on another stream keeps the batch alive with one
-    # `record_stream` and frees one block (nine of each cost the training thread 0.25 ms per step: scripts/diag_loader_gap.py)
-    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}          # (every entry starts on a 256-byte boundary)
-    flat = torch.empty(sum(sizes.values()), device=dev, dtype=torch.float32)
-    out, off = {}, 0
-    for k, shp in shapes.items():
-        out[k] = flat[off:off + math.prod(shp)].view(shp)
-        off += sizes[k]
+    out = _aligned_views(shapes, kpcn.device)
     outs = (_ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]), _ptr(out["kpcn_diffuse_buffer"]),
             _ptr(out["kpcn_specular_buffer"]), _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
             _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream())
@@ -197,6 +207,15 @@ def sample_feature_size(use_g_buf=True, use_sbmc_buf=True, use_llpm_buf=False):
     return (24 if use_g_buf else 3) + (66 if use_sbmc_buf else 0) + (1 if use_llpm_buf else 0)
 
 
+def _check_sample_buffers(who, sbmc_p, llpm, h, w, s):
+    """The optional per-sample buffers beside an (h, w, s, 27) ``sbmc_s``: each is None or a contiguous fp32 device tensor of its
+    own channel count over the same pixels and samples."""
+    for name, t, c in (("sbmc_p", sbmc_p, 66), ("llpm", llpm, 37)):
+        if t is not None and (tuple(t.shape) != (h, w, s, c) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError("%s: %s should be a contiguous fp32 (%d, %d, %d, %d) device tensor, got %s"
+                             % (who, name, h, w, s, c, tuple(t.shape)))
+
+
 def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True,
                             spp=None):
     """The batch dictionary of the SBMC / LBMC interfaces (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and
@@ -212,10 +231,7 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
                          % (tuple(sbmc_s.shape), tuple(gt.shape)))
     if use_sbmc_buf:
         _need_cuda(sbmc_p)
-    for name, t, c in (("sbmc_p", sbmc_p if use_sbmc_buf else None, 66), ("llpm", llpm, 37)):
-        if t is not None and (tuple(t.shape) != (h, w, s, c) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda):
-            raise ValueError("assemble_sample_patches: %s should be a contiguous fp32 (%d, %d, %d, %d) device tensor, got %s"
-                             % (name, h, w, s, c, tuple(t.shape)))
+    _check_sample_buffers("assemble_sample_patches", sbmc_p if use_sbmc_buf else None, llpm, h, w, s)
     if patch < 1 or patch > h or patch > w:
         raise ValueError("assemble_sample_patches: a %d-pixel patch does not fit the %dx%d image" % (patch, h, w))
     if check_origins:
@@ -234,13 +250,7 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
     shapes["target_image"] = (b, 3, patch, patch)
-    # ONE allocation, the entries are views of it (as assemble_kpcn_patches)
-    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
-    flat = torch.empty(sum(sizes.values()), device=sbmc_s.device, dtype=torch.float32)
-    out, off = {}, 0
-    for k, shp in shapes.items():
-        out[k] = flat[off:off + math.prod(shp)].view(shp)
-        off += sizes[k]
+    out = _aligned_views(shapes, sbmc_s.device)
     ins = (_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
     outs = (patch, int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
             _ptr(out.get("paths")), _ptr(out["target_image"]), _stream())
@@ -404,11 +414,9 @@ def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=Tr
     data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the table once
     (checking a device tensor here synchronises)."""
     _need_cuda(kpcn)
-    if not origins.is_cuda:
-        raise RuntimeError("assemble_kpcn_tiles: origins must be a device tensor")
+    _need_origins("assemble_kpcn_tiles", origins)
     h, w = kpcn.shape[:2]
     assert kpcn.shape == (h, w, 44) and kpcn.is_contiguous()
-    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
     if check_origins:
         check_tile_origins(origins, h, w, patch, pad)
     b, s = origins.shape[0], 0
@@ -422,13 +430,7 @@ def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=Tr
               "kpcn_albedo": (b, 3, patch, patch)}
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
-    # ONE allocation, the entries are 256-byte aligned views of it (as assemble_kpcn_patches)
-    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
-    flat = torch.empty(sum(sizes.values()), device=kpcn.device, dtype=torch.float32)
-    out, off = {}, 0
-    for k, shp in shapes.items():
-        out[k] = flat[off:off + math.prod(shp)].view(shp)
-        off += sizes[k]
+    out = _aligned_views(shapes, kpcn.device)
     check(lib().wcmc_assemble_kpcn_tiles(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad,
                                          _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
                                          _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
@@ -448,13 +450,19 @@ def finish_frame(out_rad, kpcn, llpm, preview=False):
             or llpm.shape[3] != 37 or llpm.shape[2] < 1 or not (out_rad.is_contiguous() and kpcn.is_contiguous() and llpm.is_contiguous())):
         raise ValueError("finish_frame: out_rad should be contiguous (3, H, W), kpcn (H, W, 44) and llpm (H, W, S, 37), got %s, %s, %s"
                          % (tuple(out_rad.shape), tuple(kpcn.shape), tuple(llpm.shape)))
-    dev = kpcn.device
+    return _finish(lib().wcmc_finish_frame, "finish_frame", out_rad, kpcn, llpm, preview)
+
+
+def _finish(symbol, who, out_rad, src, llpm, preview):
+    """The closing pass of either family: ``symbol`` reads the noisy input from ``src`` (H, W, ...), whose shapes ``who`` has checked."""
+    h, w = src.shape[:2]
+    dev = src.device
     out = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
     ipt = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
     has_hit = torch.empty((h, w), device=dev, dtype=torch.float32)
     pv = [torch.empty((h, w, 3), device=dev, dtype=torch.uint8) for _ in range(2)] if preview else [None, None]
-    check(lib().wcmc_finish_frame(_ptr(out_rad), _ptr(kpcn), _ptr(llpm), h, w, llpm.shape[2], _ptr(out), _ptr(ipt), _ptr(has_hit),
-                                  _ptr(pv[0]), _ptr(pv[1]), _stream()), "finish_frame")
+    check(symbol(_ptr(out_rad), _ptr(src), _ptr(llpm), h, w, llpm.shape[2], _ptr(out), _ptr(ipt), _ptr(has_hit), _ptr(pv[0]),
+                 _ptr(pv[1]), _stream()), who)
     return (out, ipt, has_hit, pv[0], pv[1]) if preview else (out, ipt, has_hit)
 
 
@@ -468,18 +476,13 @@ def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_
     origins are data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the
     table once (checking a device tensor here synchronises)."""
     _need_cuda(sbmc_s)
-    if not origins.is_cuda:
-        raise RuntimeError("assemble_sample_tiles: origins must be a device tensor")
+    _need_origins("assemble_sample_tiles", origins)
     if sbmc_s.dim() != 4 or sbmc_s.shape[3] != 27 or sbmc_s.shape[2] < 1 or not sbmc_s.is_contiguous():
         raise ValueError("assemble_sample_tiles: sbmc_s should be contiguous (H, W, S, 27), got %s" % (tuple(sbmc_s.shape),))
     h, w, s = sbmc_s.shape[:3]
-    for name, t, c in (("sbmc_p", sbmc_p if use_sbmc_buf else None, 66), ("llpm", llpm, 37)):
-        if t is not None and (tuple(t.shape) != (h, w, s, c) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda):
-            raise ValueError("assemble_sample_tiles: %s should be a contiguous fp32 (%d, %d, %d, %d) device tensor, got %s"
-                             % (name, h, w, s, c, tuple(t.shape)))
+    _check_sample_buffers("assemble_sample_tiles", sbmc_p if use_sbmc_buf else None, llpm, h, w, s)
     if use_sbmc_buf and sbmc_p is None:
         raise ValueError("assemble_sample_tiles: use_sbmc_buf needs sbmc_p")
-    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
     if check_origins:
         check_tile_origins(origins, h, w, patch, pad, who="assemble_sample_tiles")
     b = origins.shape[0]
@@ -487,13 +490,7 @@ def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_
     shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
-    # ONE allocation, the entries are 256-byte aligned views of it (as assemble_kpcn_tiles)
-    sizes = {k: (math.prod(v) + 63) // 64 * 64 for k, v in shapes.items()}
-    flat = torch.empty(sum(sizes.values()), device=sbmc_s.device, dtype=torch.float32)
-    out, off = {}, 0
-    for k, shp in shapes.items():
-        out[k] = flat[off:off + math.prod(shp)].view(shp)
-        off += sizes[k]
+    out = _aligned_views(shapes, sbmc_s.device)
     check(lib().wcmc_assemble_sample_tiles(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
                                            ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, int(bool(use_g_buf)),
                                            int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
@@ -513,11 +510,4 @@ def finish_sample_frame(out_rad, sbmc_s, llpm, preview=False):
             or not (out_rad.is_contiguous() and sbmc_s.is_contiguous() and llpm.is_contiguous())):
         raise ValueError("finish_sample_frame: out_rad should be contiguous (3, H, W), sbmc_s (H, W, S, 27) and llpm (H, W, S, 37), "
                          "got %s, %s, %s" % (tuple(out_rad.shape), tuple(sbmc_s.shape), tuple(llpm.shape)))
-    dev = sbmc_s.device
-    out = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
-    ipt = torch.empty((h, w, 3), device=dev, dtype=torch.float32)
-    has_hit = torch.empty((h, w), device=dev, dtype=torch.float32)
-    pv = [torch.empty((h, w, 3), device=dev, dtype=torch.uint8) for _ in range(2)] if preview else [None, None]
-    check(lib().wcmc_finish_sample_frame(_ptr(out_rad), _ptr(sbmc_s), _ptr(llpm), h, w, sbmc_s.shape[2], _ptr(out), _ptr(ipt),
-                                         _ptr(has_hit), _ptr(pv[0]), _ptr(pv[1]), _stream()), "finish_sample_frame")
-    return (out, ipt, has_hit, pv[0], pv[1]) if preview else (out, ipt, has_hit)
+    return _finish(lib().wcmc_finish_sample_frame, "finish_sample_frame", out_rad, sbmc_s, llpm, preview)

@@ -109,9 +109,7 @@ class PatchBatcher:
 
     def check_origins(self, origins, h, w):
         """Windows must lie inside the image (the reference would silently return a smaller patch)."""
-        o = origins.cpu().numpy() if isinstance(origins, torch.Tensor) else np.asarray(origins)
-        if o.size and (int(o[:, 0].max()) + self.patch_size > h or int(o[:, 1].max()) + self.patch_size > w or int(o.min()) < 0):
-            raise ValueError("PatchBatcher: a %d-pixel patch origin lies outside the %dx%d image" % (self.patch_size, h, w))
+        _ops.check_patch_origins(origins, h, w, self.patch_size, who="PatchBatcher")
 
     def batch(self, kpcn, llpm, gt, origins, check=True, spp=None):
         """kpcn (H,W,44), llpm (H,W,S,37) or None, gt (H,W,9): device tensors; origins: (B,2) rows/columns (numpy or

@@ -81,32 +81,44 @@ def crop_and_composite(out_rad, noisy_input, has_hit, patch_size=128, valid_size
     return torch.where(has_hit == 0, noisy_input, out_rad)
 
 
+def _zero_pbuffers(p_buffers, h, w):
+    """The stitched P-buffers of an h x w frame, zeroed: (S, C, h, w) for the (B, S, C, P, P) of a batch, or a dict of them."""
+    if isinstance(p_buffers, dict):
+        return {key: _zero_pbuffers(v, h, w) for key, v in p_buffers.items()}
+    return torch.zeros((p_buffers.shape[1], p_buffers.shape[2], h, w), device=p_buffers.device)
+
+
+def _stitch_batches(batches, run, h, w, keep_pbuffers, patch_size, first_output=None):
+    """THE tile loop of full-frame inference: ``run(batch)`` -> ``(out, p_buffers)`` for every ``(batch, coords)`` of ``batches``
+    (``coords``: the device (B, 6) rows of the tile table), one ``ops.stitch_tiles`` launch per batch.  The P-buffers are stitched
+    with ``keep_pbuffers`` where the model returns any.  ``first_output(out)`` sees the first batch's output before it is stitched.
+    Returns ``(out_rad (3, h, w), out_path)``; out_path is None, or (S, C, h, w) / a dict of them, as the P-buffers come."""
+    from .. import ops
+    out_rad, out_path = None, None
+    for batch, coords in batches:
+        out, p_buffers = run(batch)
+        if out_rad is None:
+            out_rad = torch.zeros((3, h, w), device=out.device)
+            if first_output is not None:
+                first_output(out)
+        if not (keep_pbuffers and p_buffers is not None):
+            p_buffers = None
+        else:
+            if out_path is None:
+                out_path = _zero_pbuffers(p_buffers, h, w)
+            p_buffers = ({key: v.contiguous() for key, v in p_buffers.items()} if isinstance(p_buffers, dict)
+                         else p_buffers.contiguous())
+        ops.stitch_tiles(out, p_buffers, coords, out_rad, out_path, patch_size)
+    return out_rad, out_path
+
+
 def stitched_inference(interface, dataset, patch_size=128, use_llpm_buf=True):
     """``inference`` over a ``support.datasets.FullImageDataset`` with one ``wcmc_stitch_tiles`` launch per batch in place of
     the per-tile slice copies (bit-identical to them).  Returns ``(out_rad (3, H, W), out_path)`` on the device; out_path is
     None, or (like the P-buffers of ``validate_batch``) a dict / tensor of (S, C, H, W)."""
-    from .. import ops
     interface.to_eval_mode()
-    h, w = dataset.h, dataset.w
-    out_rad, out_path = None, None
     with torch.no_grad():
-        for batch, coords in dataset.tile_batches():
-            out, p_buffers = interface.validate_batch(batch)
-            if out_rad is None:
-                out_rad = torch.zeros((3, h, w), device=out.device)
-            if not (use_llpm_buf and p_buffers is not None):
-                p_buffers = None
-            elif out_path is None:
-                if isinstance(p_buffers, dict):
-                    out_path = {key: torch.zeros((v.shape[1], v.shape[2], h, w), device=v.device)
-                                for key, v in p_buffers.items()}
-                else:
-                    out_path = torch.zeros((p_buffers.shape[1], p_buffers.shape[2], h, w), device=p_buffers.device)
-            if p_buffers is not None:
-                p_buffers = ({k: v.contiguous() for k, v in p_buffers.items()} if isinstance(p_buffers, dict)
-                             else p_buffers.contiguous())
-            ops.stitch_tiles(out, p_buffers, coords, out_rad, out_path, patch_size)
-    return out_rad, out_path
+        return _stitch_batches(dataset.tile_batches(), interface.validate_batch, dataset.h, dataset.w, use_llpm_buf, patch_size)
 
 
 # ------------------------------------------------------------------------------- denoising a render of any size (wcmc_amd.denoise)
@@ -147,42 +159,43 @@ def denoise_frame(interface, kpcn, llpm, use_llpm_buf=True, batch_size=8, want_p
     input (H, W, 3) and the mask (H, W) -- then the stitched P-buffers ((S, C, H, W), a dict of them, or None) when
     ``want_pbuffers``, then the two uint8 previews (of ``out`` and of ``ipt``) when ``preview``.  ``times``: a dict that receives the
     seconds of 'network' (tiles, network, stitching) and 'finish', at the price of two device synchronisations, and 'tiles'."""
+    from .. import ops
+    return _denoise_tiles(
+        "denoise_frame", interface, kpcn,
+        lambda origins: ops.assemble_kpcn_tiles(kpcn, llpm if use_llpm_buf else None, origins, patch_size, pad_size,
+                                                check_origins=False),
+        lambda out_rad: ops.finish_frame(out_rad, kpcn, llpm, preview=preview),
+        batch_size, want_pbuffers, patch_size, pad_size, preview, times)
+
+
+def _denoise_tiles(who, interface, frame, assemble, finish, batch_size, want_pbuffers, patch_size, pad_size, preview, times,
+                   check_output=False):
+    """THE frame driver behind ``denoise_frame`` and ``denoise_sample_frame`` (``who``): the tile table of ``frame``, a device buffer (H, W, ...)
+    of the family, and its host checks, ``_stitch_batches`` over ``assemble(origins)`` -- the family's batch for a device (B, 2) slice of the tile
+    origins -- and ``interface.denoise_batch``, then ``finish(out_rad)``, the family's closing op, and the return tuple.
+    ``check_output``: ``check_output_size`` on the first batch's output.  A third model family supplies the two closures."""
     import time
     from .. import ops
-    h, w = kpcn.shape[:2]
+    (h, w), device = frame.shape[:2], frame.device
     coords = frame_tiles(h, w, patch_size, pad_size)
     ops.check_tile_coords(coords, h, w, patch_size)
-    ops.check_tile_origins([c[4:6] for c in coords], h, w, patch_size, pad_size, who="denoise_frame")
+    ops.check_tile_origins([c[4:6] for c in coords], h, w, patch_size, pad_size, who=who)
     interface.to_eval_mode()
     if times is not None:
-        torch.cuda.synchronize(kpcn.device)
+        torch.cuda.synchronize(device)
         t0 = time.perf_counter()
     with torch.no_grad():
-        coords_dev = torch.tensor(coords, dtype=torch.int32, device=kpcn.device)
+        coords_dev = torch.tensor(coords, dtype=torch.int32, device=device)
         origins_dev = coords_dev[:, 4:6].contiguous()
-        out_rad = torch.zeros((3, h, w), device=kpcn.device)
-        out_path = None
-        for k in range(0, len(coords), batch_size):
-            batch = ops.assemble_kpcn_tiles(kpcn, llpm if use_llpm_buf else None, origins_dev[k:k + batch_size], patch_size, pad_size,
-                                            check_origins=False)
-            out, p_buffers = interface.denoise_batch(batch)
-            if not (want_pbuffers and p_buffers is not None):
-                p_buffers = None
-            else:
-                if out_path is None:
-                    if isinstance(p_buffers, dict):
-                        out_path = {key: torch.zeros((v.shape[1], v.shape[2], h, w), device=v.device) for key, v in p_buffers.items()}
-                    else:
-                        out_path = torch.zeros((p_buffers.shape[1], p_buffers.shape[2], h, w), device=p_buffers.device)
-                p_buffers = ({key: v.contiguous() for key, v in p_buffers.items()} if isinstance(p_buffers, dict)
-                             else p_buffers.contiguous())
-            ops.stitch_tiles(out, p_buffers, coords_dev[k:k + batch_size], out_rad, out_path, patch_size)
+        batches = ((assemble(origins_dev[k:k + batch_size]), coords_dev[k:k + batch_size]) for k in range(0, len(coords), batch_size))
+        first = (lambda out: check_output_size(out.shape[2], out.shape[3], patch_size, pad_size)) if check_output else None
+        out_rad, out_path = _stitch_batches(batches, interface.denoise_batch, h, w, want_pbuffers, patch_size, first)
         if times is not None:
-            torch.cuda.synchronize(kpcn.device)
+            torch.cuda.synchronize(device)
             t1 = time.perf_counter()
-        res = ops.finish_frame(out_rad, kpcn, llpm, preview=preview)
+        res = finish(out_rad)
         if times is not None:
-            torch.cuda.synchronize(kpcn.device)
+            torch.cuda.synchronize(device)
             times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=len(coords))
     return res[:3] + ((out_path,) if want_pbuffers else ()) + (tuple(res[3:]) if preview else ())
 
@@ -206,40 +219,10 @@ def denoise_sample_frame(interface, sbmc_s, sbmc_p, llpm, use_llpm_buf=True, use
     The denoiser's receptive field is the caller's: an output so small that replicated pixels would reach an owned window is a
     ``ValueError`` after the first batch (``check_output_size``).  Returns what ``denoise_frame`` returns; the P-buffer is one
     (S, C, H, W) tensor."""
-    import time
     from .. import ops
-    h, w = sbmc_s.shape[:2]
-    coords = frame_tiles(h, w, patch_size, pad_size)
-    ops.check_tile_coords(coords, h, w, patch_size)
-    ops.check_tile_origins([c[4:6] for c in coords], h, w, patch_size, pad_size, who="denoise_sample_frame")
-    interface.to_eval_mode()
-    if times is not None:
-        torch.cuda.synchronize(sbmc_s.device)
-        t0 = time.perf_counter()
-    with torch.no_grad():
-        coords_dev = torch.tensor(coords, dtype=torch.int32, device=sbmc_s.device)
-        origins_dev = coords_dev[:, 4:6].contiguous()
-        out_rad = torch.zeros((3, h, w), device=sbmc_s.device)
-        out_path = None
-        for k in range(0, len(coords), batch_size):
-            batch = ops.assemble_sample_tiles(sbmc_s, sbmc_p if use_sbmc_buf else None, llpm if use_llpm_buf else None,
-                                              origins_dev[k:k + batch_size], patch_size, pad_size, use_g_buf, use_sbmc_buf,
-                                              check_origins=False)
-            out, p_buffer = interface.denoise_batch(batch)
-            if k == 0:
-                check_output_size(out.shape[2], out.shape[3], patch_size, pad_size)
-            if not (want_pbuffers and p_buffer is not None):
-                p_buffer = None
-            else:
-                if out_path is None:
-                    out_path = torch.zeros((p_buffer.shape[1], p_buffer.shape[2], h, w), device=p_buffer.device)
-                p_buffer = p_buffer.contiguous()
-            ops.stitch_tiles(out, p_buffer, coords_dev[k:k + batch_size], out_rad, out_path, patch_size)
-        if times is not None:
-            torch.cuda.synchronize(sbmc_s.device)
-            t1 = time.perf_counter()
-        res = ops.finish_sample_frame(out_rad, sbmc_s, llpm, preview=preview)
-        if times is not None:
-            torch.cuda.synchronize(sbmc_s.device)
-            times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=len(coords))
-    return res[:3] + ((out_path,) if want_pbuffers else ()) + (tuple(res[3:]) if preview else ())
+    return _denoise_tiles(
+        "denoise_sample_frame", interface, sbmc_s,
+        lambda origins: ops.assemble_sample_tiles(sbmc_s, sbmc_p if use_sbmc_buf else None, llpm if use_llpm_buf else None, origins,
+                                                  patch_size, pad_size, use_g_buf, use_sbmc_buf, check_origins=False),
+        lambda out_rad: ops.finish_sample_frame(out_rad, sbmc_s, llpm, preview=preview),
+        batch_size, want_pbuffers, patch_size, pad_size, preview, times, check_output=True)

@@ -204,90 +204,80 @@ class _FrameStream:
         self._scratch_p = None                                        # sample-based without sbmc_p: one band's unread out_p (flat)
 
     def _frame(self, fn, ring, stop):
-        """Enqueue one frame on the copy stream; ``(buffers, before_end, after_end)`` or None when the consumer has gone."""
+        """Enqueue one frame on the copy stream; ``(buffers, before_end, after_end)`` or None when the consumer has gone.  THE band
+        loop, for every model family: what differs between them is in ``_kpcn_family`` / ``_sample_family``."""
         from .. import ops
         from ..denoise import read_raw
         parts, spp = read_raw(fn, self.spp)
         h, w = parts[0].shape[:2]
-        if self.base_model != 'kpcn':
-            return self._sample_frame(parts, spp, h, w, ring, stop)
         band_rows = min(h, self.band_rows or default_band_rows(h, w, spp, self.target_bytes))
         reader = BandReader(parts, band_rows, self.workers, ring=ring, stop=stop)
         bands, seen = iter(reader), 0
         try:
             with torch.cuda.stream(self.copy_stream):
-                kpcn, ws = ops.preprocess_kpcn_begin(h, w, self.device)
-                llpm = torch.empty((h, w, spp, 7 + 5 * (self.max_depth + 1)), device=self.device, dtype=torch.float32)
-                n = band_rows * w * spp * RAW_C
-                if self._band is None or self._band.numel() < n:
-                    self._band = None                                 # (used on this stream alone: the allocator may reuse it at once)
-                    self._band = torch.empty(n, device=self.device, dtype=torch.float32)
+                family = self._kpcn_family if self.base_model == 'kpcn' else self._sample_family
+                bufs, on_band, end = family(h, w, spp, band_rows)
+                band = self._flat('_band', band_rows * w * spp * RAW_C)
                 for slot, row0, rows in bands:
                     shape = (rows, w, spp, RAW_C)
-                    d_band = self._band[:math.prod(shape)].view(shape)
+                    d_band = band[:math.prod(shape)].view(shape)
                     d_band.copy_(ring.view(slot, shape), non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                     ring.release(slot, ev)                            # (the event guards the pinned slot's reuse)
                     ops.sanitize_(d_band)
-                    ops.preprocess_kpcn_rows(d_band, row0, kpcn, ws, self.max_depth)
-                    ops.preprocess_llpm(d_band, self.max_depth, out=llpm[row0:row0 + rows])
+                    on_band(d_band, row0, rows)
                     self.bytes_moved += d_band.numel() * 4
                     seen += 1
                 if seen < len(reader.ranges):                         # the reader gave up: the stop flag is set
                     return None
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record(self.copy_stream)
-                ops.preprocess_kpcn_end(kpcn, ws, spp)
+                if end is not None:                                   # (no finish pass: the pair brackets nothing)
+                    end()
                 ev1.record(self.copy_stream)
         finally:
             bands.close()
-        return (kpcn, llpm), ev0, ev1
+        return bufs, ev0, ev1
 
-    def _sample_frame(self, parts, spp, h, w, ring, stop):
-        """``_frame`` for the sample-based models: ``((sbmc_s, sbmc_p or None, llpm), event, event)``.  Every buffer is per sample, so a
-        band is final when its kernels have run: no begin / end, no workspace.  ``wcmc_preprocess_sbmc`` writes both of its outputs;
-        without ``use_sbmc_buf`` the second goes to a band-sized scratch that the next band overwrites."""
+    def _flat(self, name, n):
+        """The flat device buffer ``self.<name>``, grown to at least ``n`` floats.  The old one is dropped before the new one is
+        allocated: it is used on the copy stream alone, so the allocator may reuse it at once."""
+        if getattr(self, name) is None or getattr(self, name).numel() < n:
+            setattr(self, name, None)
+            setattr(self, name, torch.empty(n, device=self.device, dtype=torch.float32))
+        return getattr(self, name)
+
+    # What a model family supplies to ``_frame``, called on the copy stream for a frame of (h, w, spp) in bands of ``band_rows``: it
+    # allocates the frame's buffers and returns ``(buffers, on_band(d_band, row0, rows), end() or None)`` -- what to run on one sanitised
+    # band, and what closes the frame between the two timing events.
+    def _kpcn_family(self, h, w, spp, band_rows):
+        """``(kpcn, llpm)``: the statistics of a band go to the (h, w) workspace, ``preprocess_kpcn_end`` closes the frame."""
         from .. import ops
-        band_rows = min(h, self.band_rows or default_band_rows(h, w, spp, self.target_bytes))
-        reader = BandReader(parts, band_rows, self.workers, ring=ring, stop=stop)
-        bands, seen = iter(reader), 0
+        kpcn, ws = ops.preprocess_kpcn_begin(h, w, self.device)
+        llpm = torch.empty((h, w, spp, 7 + 5 * (self.max_depth + 1)), device=self.device, dtype=torch.float32)
+
+        def on_band(d_band, row0, rows):
+            ops.preprocess_kpcn_rows(d_band, row0, kpcn, ws, self.max_depth)
+            ops.preprocess_llpm(d_band, self.max_depth, out=llpm[row0:row0 + rows])
+        return (kpcn, llpm), on_band, lambda: ops.preprocess_kpcn_end(kpcn, ws, spp)
+
+    def _sample_family(self, h, w, spp, band_rows):
+        """``(sbmc_s, sbmc_p or None, llpm)``.  Every buffer is per sample, so a band is final when its kernels have run: no begin /
+        end, no workspace.  ``wcmc_preprocess_sbmc`` writes both of its outputs; without ``use_sbmc_buf`` the second goes to a
+        band-sized scratch that the next band overwrites."""
+        from .. import ops
         pc = 11 * (self.max_depth + 1)
-        try:
-            with torch.cuda.stream(self.copy_stream):
-                new = lambda c: torch.empty((h, w, spp, c), device=self.device, dtype=torch.float32)   # noqa: E731
-                sbmc_s, llpm = new(27), new(7 + 5 * (self.max_depth + 1))
-                sbmc_p = new(pc) if self.use_sbmc_buf else None
-                n = band_rows * w * spp * RAW_C
-                if self._band is None or self._band.numel() < n:
-                    self._band = None
-                    self._band = torch.empty(n, device=self.device, dtype=torch.float32)
-                n = 0 if self.use_sbmc_buf else band_rows * w * spp * pc
-                if self._scratch_p is None or self._scratch_p.numel() < n:
-                    self._scratch_p = None
-                    self._scratch_p = torch.empty(n, device=self.device, dtype=torch.float32)
-                for slot, row0, rows in bands:
-                    shape = (rows, w, spp, RAW_C)
-                    d_band = self._band[:math.prod(shape)].view(shape)
-                    d_band.copy_(ring.view(slot, shape), non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self.copy_stream)
-                    ring.release(slot, ev)                            # (the event guards the pinned slot's reuse)
-                    ops.sanitize_(d_band)
-                    out_p = (sbmc_p[row0:row0 + rows] if self.use_sbmc_buf
-                             else self._scratch_p[:rows * w * spp * pc].view(rows, w, spp, pc))
-                    ops.preprocess_sbmc(d_band, self.max_depth, out_s=sbmc_s[row0:row0 + rows], out_p=out_p)
-                    ops.preprocess_llpm(d_band, self.max_depth, out=llpm[row0:row0 + rows])
-                    self.bytes_moved += d_band.numel() * 4
-                    seen += 1
-                if seen < len(reader.ranges):                         # the reader gave up: the stop flag is set
-                    return None
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record(self.copy_stream)                          # (no finish pass: the pair brackets nothing)
-                ev1.record(self.copy_stream)
-        finally:
-            bands.close()
-        return (sbmc_s, sbmc_p, llpm), ev0, ev1
+        new = lambda c: torch.empty((h, w, spp, c), device=self.device, dtype=torch.float32)   # noqa: E731
+        sbmc_s, llpm = new(27), new(7 + 5 * (self.max_depth + 1))
+        sbmc_p = new(pc) if self.use_sbmc_buf else None
+        scratch = None if self.use_sbmc_buf else self._flat('_scratch_p', band_rows * w * spp * pc)
+
+        def on_band(d_band, row0, rows):
+            out_p = sbmc_p[row0:row0 + rows] if self.use_sbmc_buf else scratch[:rows * w * spp * pc].view(rows, w, spp, pc)
+            ops.preprocess_sbmc(d_band, self.max_depth, out_s=sbmc_s[row0:row0 + rows], out_p=out_p)
+            ops.preprocess_llpm(d_band, self.max_depth, out=llpm[row0:row0 + rows])
+        return (sbmc_s, sbmc_p, llpm), on_band, None
 
     def _produce(self, out_q, permits, stop):
         try:
