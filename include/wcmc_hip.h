@@ -327,6 +327,47 @@ int wcmc_kernel_apply_bwd(const float* logits, int64_t lsn, int64_t lsh, int64_t
                           float* d_logits, int64_t qsn, int64_t qsh, int64_t qsw,
                           float* d_data, int N, int C, int h, int w, int k, void* stream);
 
+/* ---------------------------------------------------------------- kernel splat
+ * Replaces sbmc.modules.KernelApply(softmax=True, splat=True) and the per-sample step of
+ * sbmc.modules.ProgressiveKernelApply(splat=True) inside sbmc.Multisteps (upstream: the Halide
+ * ops Scatter2Gather + KernelWeighting).  Specification: DESIGN.md section 18.
+ *   logits: NHWC view (N,h,w,k2), k2 = k*k, k odd, k <= 21 -- tap t = (dy+r)*k + (dx+r), r = k/2.
+ *   data: (N,C,h,w) with arbitrary element strides (sn,sc,sh,sw), C <= 4.
+ *   A source pixel q sends tap t to the destination q + (dy,dx); destinations outside the image are dropped:
+ *     sum_r[n,c,p] (+)= sum over (q,t), q + off(t) = p, of w[n,q,t] * data[n,c,q],   sum_w[n,p] (+)= the same sum of w,
+ *     w[n,q,t] = exp(logits[n,q,t] - m) * s
+ *       mode WCMC_SPLAT_SOFTMAX: m = max_t logits[n,q,:], s = 1 / sum_t exp(logits[n,q,t] - m); lse [N*h*w] receives the
+ *                                per-source log-sum-exp for the backward (may be NULL);
+ *       mode WCMC_SPLAT_SHIFT:   m = shift[n] (device, (N,)), s = 1.
+ *   sum_r (N,C,h,w) and sum_w (N,h,w) are contiguous; accumulate = 0 overwrites them, else they are added into.
+ *   Two launches and no atomics: every sum has a fixed order, the results are bitwise reproducible.
+ *   workspace: wcmc_kernel_splat_fwd_workspace_bytes(N, C, h, w, k2) bytes (0 for an unsupported shape).
+ */
+enum wcmc_splat_mode { WCMC_SPLAT_SOFTMAX = 0, WCMC_SPLAT_SHIFT = 1 };
+size_t wcmc_kernel_splat_fwd_workspace_bytes(int N, int C, int h, int w, int k2);
+int wcmc_kernel_splat_fwd(const float* logits, int64_t lsn, int64_t lsh, int64_t lsw,
+                          const float* data, int64_t dsn, int64_t dsc, int64_t dsh, int64_t dsw,
+                          float* sum_r, float* sum_w, float* lse, int mode, const float* shift,
+                          int accumulate, void* workspace, size_t workspace_bytes,
+                          int N, int C, int h, int w, int k2, void* stream);
+/* G[q,t] = sum_c data[c,q] * g_r[c,q+off(t)] + g_w[q+off(t)] (0 outside); either of g_r (N,C,h,w strided) and g_w
+ * (N,h,w strided) may be NULL, not both.
+ *   d_data[c,q]   = sum_t w[q,t] * g_r[c,q+off(t)]           ((N,C,h,w) contiguous, written, may be NULL)
+ *   d_logits[q,t] = w * G (shift mode),  w * (G - sum_u w[q,u] G[q,u]) (softmax mode; lse as the forward wrote it)
+ * Both are gathers around the source pixel: no atomics, bitwise reproducible. */
+int wcmc_kernel_splat_bwd(const float* logits, int64_t lsn, int64_t lsh, int64_t lsw,
+                          const float* data, int64_t dsn, int64_t dsc, int64_t dsh, int64_t dsw,
+                          const float* g_r, int64_t gsn, int64_t gsc, int64_t gsh, int64_t gsw,
+                          const float* g_w, int64_t wsn, int64_t wsh, int64_t wsw,
+                          const float* lse, int mode, const float* shift,
+                          float* d_logits, int64_t qsn, int64_t qsh, int64_t qsw,
+                          float* d_data, int N, int C, int h, int w, int k2, void* stream);
+/* out[n] = max over (t,y,x) of logits[n] (``kernels.amax(dim=(1, 2, 3))``: a NaN logit gives NaN), the running shift of
+ * ProgressiveKernelApply.  Two launches in a fixed order; workspace: wcmc_logit_max_workspace_bytes(N). */
+size_t wcmc_logit_max_workspace_bytes(int N);
+int wcmc_logit_max(const float* logits, int64_t lsn, int64_t lsh, int64_t lsw, float* out,
+                   void* workspace, size_t workspace_bytes, int N, int h, int w, int k2, void* stream);
+
 /* Tail of sbmc.KPCN.forward (result keys consumed at support/interfaces.py:207-211):
  *   radiance = albedo * r_diffuse + exp(r_specular) - 1.
  * Inputs (N,C,H,W) with arbitrary element strides; out / grad_out / d_* contiguous (N,C,H,W). */

@@ -6,4 +6,4 @@ external ``sbmc`` package.  All arithmetic runs in ``libwcmc_hip.so`` (``include
 """
 from . import ops  # noqa: F401
 from .models import KPCN  # noqa: F401
-from .modules import Autoencoder, ConvChain, KernelApply  # noqa: F401
+from .modules import Autoencoder, ConvChain, KernelApply, ProgressiveKernelApply  # noqa: F401

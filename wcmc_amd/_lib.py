@@ -58,6 +58,12 @@ SIGNATURES = {
     "wcmc_kernel_apply_fwd": (I, [P, L, L, L, P, L, L, L, L, P, L, L, L, L, P, I, I, I, I, I, P]),
     "wcmc_kernel_apply_bwd": (I, [P, L, L, L, P, L, L, L, L, P, L, L, L, L, P, L, L, L, L, P,
                                   P, L, L, L, P, I, I, I, I, I, P]),
+    "wcmc_kernel_splat_fwd_workspace_bytes": (Z, [I, I, I, I, I]),
+    "wcmc_kernel_splat_fwd": (I, [P, L, L, L, P, L, L, L, L, P, P, P, I, P, I, P, Z, I, I, I, I, I, P]),
+    "wcmc_kernel_splat_bwd": (I, [P, L, L, L, P, L, L, L, L, P, L, L, L, L, P, L, L, L, P, I, P,
+                                  P, L, L, L, P, I, I, I, I, I, P]),
+    "wcmc_logit_max_workspace_bytes": (Z, [I]),
+    "wcmc_logit_max": (I, [P, L, L, L, P, P, Z, I, I, I, I, P]),
     "wcmc_recombine_fwd": (I, [P, L, L, L, L, P, L, L, L, L, P, L, L, L, L, P, I, I, I, I, P]),
     "wcmc_image_loss_workspace_bytes": (Z, []),
     "wcmc_image_loss_fwd": (I, [P, L, L, L, L, P, L, L, L, L, F, P, P, P, Z, I, I, I, I, P]),

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .support.utils import crop_like
 
 
 class _WeightNormConv(nn.Module):
@@ -187,11 +188,45 @@ class Autoencoder(nn.Module):
 
 
 class KernelApply(nn.Module):
-    """``sbmc.modules.KernelApply(softmax=True, splat=False)``; returns the tensor only."""
+    """``sbmc.modules.KernelApply(softmax=True, splat=...)``; returns the tensor only.  ``splat=False``: the gather of the KPCN
+    path.  ``splat=True``: every source pixel's softmax kernel is splatted (``ops.kernel_splat``), ``data`` cropped to
+    ``kernels`` as a view, and the result is ``sum_r / (sum_w + 1e-8)``."""
 
     def __init__(self, softmax=True, splat=False):
         super().__init__()
-        assert softmax and not splat, "only the softmax gather form is on the KPCN path"
+        assert softmax, "only softmax kernels are built (softmax=False is not)"
+        self.splat = splat
 
     def forward(self, data, kernels):
-        return ops.kernel_apply(data, kernels)
+        if not self.splat:
+            return ops.kernel_apply(data, kernels)
+        sum_r, sum_w = ops.kernel_splat(crop_like(data, kernels), kernels)
+        return sum_r / (sum_w.unsqueeze(1) + 1e-8)
+
+
+class ProgressiveKernelApply(nn.Module):
+    """``sbmc.modules.ProgressiveKernelApply(splat=True)``: one sample's splat added into running sums that share one shift per
+    image, ``(sum_r, sum_w, max_w) = self(data, kernels, sum_r, sum_w, max_w)`` with ``None`` for all three on the first call.
+    The weights are ``exp(kernels - max_w[n])`` with ``max_w`` the running per-image maximum of the logits (detached); when it
+    moves, the sums are rescaled by ``exp(old - new)``.  The caller divides ``sum_r / (sum_w + 1e-8)`` at the end; that ratio does
+    not depend on the shift."""
+
+    def __init__(self, splat=True):
+        super().__init__()
+        assert splat, "only the splatting form is built (splat=False is not)"
+
+    def forward(self, data, kernels, sum_r, sum_w, max_w):
+        kernels = ops.as_nhwc(kernels)                              # once, for both launches
+        data = crop_like(data, kernels)
+        kmax = ops.logit_max(kernels)
+        if max_w is None:
+            assert sum_r is None and sum_w is None, "the first call starts all three of sum_r, sum_w and max_w"
+            return ops.kernel_splat(data, kernels, shift=kmax) + (kmax,)
+        new = torch.maximum(max_w, kmax)
+        scale = torch.exp(max_w - new)                              # three or four floats per pixel: torch, under autograd
+        if sum_w.dim() == 4:                                        # (N, 1, h, w) sums of weights are taken and given back as such
+            r, w = ops.kernel_splat(data, kernels, shift=new, into=(sum_r * scale.view(-1, 1, 1, 1),
+                                                                    sum_w.squeeze(1) * scale.view(-1, 1, 1)))
+            return r, w.unsqueeze(1), new
+        r, w = ops.kernel_splat(data, kernels, shift=new, into=(sum_r * scale.view(-1, 1, 1, 1), sum_w * scale.view(-1, 1, 1)))
+        return r, w, new

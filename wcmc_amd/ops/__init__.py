@@ -161,6 +161,7 @@ from .pathnet_fused import (_dense_pixel_stride, _EmbedSppMeanFusedX, _FinalFuse
                             _note_unfused, conv_chain_spp_mean, cat_broadcast_chain)
 from .image import (_KernelApply, kernel_apply, chain_kernel_apply, _Recombine, recombine, _image_loss_raw, _L1Mean, l1_mean,  # noqa: E402,F401
                     image_metrics, relative_mse, LOSS2_KINDS, _ImageLoss2, image_loss2, image_eval)
+from .splat import (SPLAT_SOFTMAX, SPLAT_SHIFT, _splat_dims, _KernelSplat, kernel_splat, logit_max)  # noqa: E402,F401
 from .manifold import (_FeatureMSE, _GRS, grs_loss, feature_mse)  # noqa: E402,F401
 from .optim import (clip_grad_norm_, clip_adam_, clip_adam_hyper, clip_adam_dev_, step_guard_, step_guard_local_,  # noqa: E402,F401
                     step_guard_global_)
