@@ -763,6 +763,28 @@ int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const f
 int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S, float* out,
                              float* ipt, float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
 
+/* ---------------------------------------------------------------- filtering a frame by its P-buffer (csrc/pbuffer_filter.hip)
+ * Non-local means whose patch distance is taken between the per-pixel statistics of the path embedding (Ray Histogram Fusion with
+ * the learned manifold in place of the colour histograms).  The build's own specification: DESIGN.md section 19.
+ *   image (H,W,Cr), element (y,x,c) at image[y*ish + x*isw + c*isc], Cr <= 4; p_buffer (S,C,H,W), element (s,c,y,x) at
+ *   p_buffer[s*pss + c*psc + y*psh + x*psw], S >= 1, 1 <= C <= 32; mask (H,W) contiguous or NULL, mask_bytes = 1 (uint8 / bool)
+ *   or 4 (fp32), a pixel counts where its element is not zero.
+ *     mu[c,p] = (1/S) sum_s P[s,c,p],   v[c,p] = (1/S^2) sum_s (P[s,c,p] - mu[c,p])^2            (sample order, fp32)
+ *     delta(p,q) = (1/C) sum_c (mu[c,p] - mu[c,q])^2 / (eps + v[c,p] + v[c,q])
+ *     D(p,q) = mean of delta(p+o, q+o) over |oy|,|ox| <= f with p+o and q+o inside the image
+ *     w(p,q) = exp(-D(p,q) / bandwidth^2), q = p + (dy,dx), |dy|,|dx| <= R, q inside the image and mask[q] != 0; else 0
+ *     wsum[p] = sum_q w(p,q);  out[p,:] = sum_q w(p,q) image[q,:] / wsum[p]   (q in tap order, dy major: bitwise reproducible)
+ *     where mask[p] == 0: out[p,:] = image[p,:], wsum[p] = 0.
+ *   out (H,W,Cr) and wsum (H,W) are contiguous.  0 <= R <= 10, 0 <= f <= 3, bandwidth > 0, eps > 0.  A non-finite P-buffer
+ *   value poisons the pixels whose windows and patches read it, and no others.
+ *   workspace: wcmc_pbuffer_filter_workspace_bytes(S, C, H, W) bytes (0 for an unsupported shape); it receives {mu, v}.
+ *   passes: 1 the statistics launch alone, 2 the filter launch alone (the workspace holds the statistics), 3 both. */
+size_t wcmc_pbuffer_filter_workspace_bytes(int S, int C, int H, int W);
+int wcmc_pbuffer_filter(const float* image, int64_t ish, int64_t isw, int64_t isc,
+                        const float* p_buffer, int64_t pss, int64_t psc, int64_t psh, int64_t psw,
+                        const void* mask, int mask_bytes, float* out, float* wsum, void* workspace, size_t workspace_bytes,
+                        int H, int W, int S, int C, int Cr, int R, int f, float bandwidth, float eps, int passes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,8 @@ SIGNATURES = {
     "wcmc_finish_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
     "wcmc_assemble_sample_tiles": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P]),
     "wcmc_finish_sample_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
+    "wcmc_pbuffer_filter_workspace_bytes": (Z, [I, I, I, I]),
+    "wcmc_pbuffer_filter": (I, [P, L, L, L, P, L, L, L, L, P, I, P, P, P, Z, I, I, I, I, I, I, I, F, F, I, P]),
 }
 
 _lib = None

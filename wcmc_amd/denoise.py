@@ -1,7 +1,7 @@
 """Denoise raw renders of any size with a trained KPCN, SBMC or LBMC model: no ground truth, no offline files, every pixel.
 
     python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
-        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
+        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--rhf] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
     python -m wcmc_amd.denoise ... --model_name SBMC_manifold --denoiser my_pkg.models:make_multisteps [--use_sbmc_buf] [--tile_pad N]
 
 Per input file (renderer output (H, W, S, 104), H and W at least 64): the first ``--spp`` samples (default: what the file holds; a
@@ -10,7 +10,9 @@ sanitised and preprocessed there band by band (``support.staging.FrameStreamer``
 memory, and the next file's bands cross while this one's network runs; ``--band_rows`` bounds the pinned memory);
 ``support.inference.denoise_frame`` runs the network over mirror-extended tiles and composites the result;
 ``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the result
-and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  The model flags are those of
+and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  ``--rhf`` filters the noisy input by the stitched
+P-buffer (``wcmc_amd.rhf``; ``--rhf_radius``, ``--rhf_patch_radius``, ``--rhf_bandwidth``, ``--rhf_eps``) with ``has_hit`` as the mask and
+writes ``<stem>_rhf.npy`` and the neighbour count ``<stem>_rhf_neighbours.npy`` (PNGs with ``--png``).  The model flags are those of
 ``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  One line per frame reports the seconds of each phase.
 
 A model whose name holds ``SBMC`` / ``LBMC`` is a ``train_sbmc`` / ``train_lbmc`` checkpoint around the caller's base denoiser
@@ -27,7 +29,7 @@ import zlib
 import numpy as np
 import torch
 
-from . import ops, train_kpcn
+from . import ops, rhf, train_kpcn
 from .support.datasets import MAX_CONTINUATIONS, dncnn_in_size
 from .support.inference import denoise_frame, denoise_sample_frame, frame_tiles
 from .support.staging import FrameStreamer
@@ -169,14 +171,16 @@ def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, prepro
     h, w, spp = llpm.shape[:3]
     batch_size = tile_batch_size(spp, args.tile_batch)
     times = {}
+    want_rhf = getattr(args, 'rhf', False)
+    want_p = args.save_pbuffer or want_rhf
     if sample_launcher(args.model_name) is not None:
         res = denoise_sample_frame(interface, bufs[0], bufs[1], llpm, args.use_llpm_buf, args.use_g_buf, args.use_sbmc_buf,
-                                   batch_size, want_pbuffers=args.save_pbuffer, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
+                                   batch_size, want_pbuffers=want_p, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
                                    preview=args.png, times=times)
     else:
-        res = denoise_frame(interface, bufs[0], llpm, args.use_llpm_buf, batch_size, want_pbuffers=args.save_pbuffer,
+        res = denoise_frame(interface, bufs[0], llpm, args.use_llpm_buf, batch_size, want_pbuffers=want_p,
                             patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
-    out, out_path = res[0], (res[3] if args.save_pbuffer else None)
+    out, out_path = res[0], (res[3] if want_p else None)
     os.makedirs(output_dir, exist_ok=True)
     img = out.cpu().numpy()
     np.save(os.path.join(output_dir, stem + '_denoised.npy'), img)
@@ -190,6 +194,11 @@ def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, prepro
             raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
         p = out_path['diffuse'] if isinstance(out_path, dict) else out_path
         np.save(os.path.join(output_dir, stem + '_pbuffer.npy'), p.permute(2, 3, 0, 1).cpu().numpy())
+    if want_rhf:
+        if out_path is None:
+            raise ValueError("--rhf: the model computes no P-buffer (it needs --use_llpm_buf)")
+        f_out, f_wsum = rhf.rhf_filter(res[1], out_path, res[2], **rhf_arguments(args))
+        rhf.write_outputs(output_dir, stem, f_out, f_wsum, args.rhf_radius, png=args.png)
     times.update(upload=upload, preprocess=preprocess, write=time.perf_counter() - t1 - times['network'] - times['finish'])
     print("%s: %d x %d, %d spp, tiles of %d per call: upload %.3f s, preprocess %.3f s, network %.3f s, finish %.3f s"
           % (stem, h, w, spp, batch_size, times['upload'], times['preprocess'], times['network'], times['finish']))
@@ -273,11 +282,20 @@ def build_parser():
                         'bands are pinned on the host, one lies on the device, and the result does not depend on it')
     p.add_argument('--png', action='store_true', help='also write 8-bit tone-mapped <stem>_denoised.png and <stem>_input.png')
     p.add_argument('--save_pbuffer', action='store_true', help='also write the stitched P-buffer <stem>_pbuffer.npy (H, W, S, C)')
+    p.add_argument('--rhf', action='store_true',
+                   help='also filter the noisy input by the stitched P-buffer (wcmc_amd.rhf) and write <stem>_rhf.npy and the '
+                        'neighbour count <stem>_rhf_neighbours.npy, PNGs with --png; needs --use_llpm_buf')
+    rhf.add_filter_arguments(p, prefix='rhf_')
     add_sample_arguments(p)
     p.add_argument('--tile_pad', type=int, default=PAD_SIZE, metavar='N',
                    help='overlap of the 128-pixel tiles on each side (SBMC / LBMC: at least what the denoiser\'s receptive field '
                         'takes off a side of a tile; KPCN models: 32)')
     return p
+
+
+def rhf_arguments(args):
+    """The filter's parameters from the ``--rhf_*`` flags, checked."""
+    return rhf.check_filter_arguments(args.rhf_radius, args.rhf_patch_radius, args.rhf_bandwidth, args.rhf_eps, flag='--rhf_')
 
 
 def add_sample_arguments(p):
@@ -307,6 +325,10 @@ def check_inputs(args):
         tile_batch_size(spp, args.tile_batch)
     if args.save_pbuffer and not args.use_llpm_buf:
         raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
+    if getattr(args, 'rhf', False):
+        if not args.use_llpm_buf:
+            raise ValueError("--rhf: the model computes no P-buffer (it needs --use_llpm_buf)")
+        rhf_arguments(args)
     return args
 
 
