@@ -691,6 +691,34 @@ int wcmc_assemble_sample_patches_prefix(const float* sbmc_s, const float* sbmc_p
                                         int use_sbmc_buf, float* radiance, float* features, float* paths, float* target_image,
                                         void* stream);
 
+/* ---------------------------------------------------------------- dihedral patch augmentation
+ * wcmc_assemble_kpcn_patches_aug / wcmc_assemble_sample_patches_aug: the `_prefix` entry points with one transform code per patch,
+ *   transforms = B device ints.  Code t in 0..7 is T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) (numpy's rot90 and fliplr on
+ *   the row and column axes); 0 is the identity, and the eight codes are the dihedral group of the square -- what the reference's
+ *   _random_rot(_random_flip(.)) (support/datasets.py:718-758) reaches, every element by two of its sixteen draws.  origins keep
+ *   their meaning: they name a P x P window of the source frame, and batch entry b is T_t[b] of that window, as if the whole frame
+ *   had been transformed before preprocessing:
+ *     - every per-pixel channel (values and variances of the five KPCN groups, depth and its variance, path weight, paths, the three
+ *       buffers, albedo, the three targets; every channel of radiance / features / paths / target_image) is that of the source pixel;
+ *     - the x- and y-differences of the diffuse, specular, normal and albedo values and of the depth are taken again from the stored
+ *       value channels: dx_out(y, x) = val(src(y, x)) - val(src(y, x - 1)), dy_out(y, x) = val(src(y, x)) - val(src(y - 1, x)), one
+ *       fp32 subtraction of two stored floats, where src is the same affine map (at x = 0 / y = 0: one step outside the window), and
+ *       exactly 0.f where that neighbour lies outside the frame (the transformed frame's first column / row, as _gradients);
+ *     - direction-valued channels (normals, subpixel, light directions) are copied, not re-expressed: the reference's functions do the
+ *       same.
+ *   With all codes 0 the batch is the `_prefix` entry point's bit for bit.  The codes are data: the host checks them (ops.
+ *   check_patch_transforms) and the kernels mask them to t & 7, so a bad table cannot read outside the buffers.
+ *   WCMC_ERR_BAD_ARG before any launch: null transforms; another null pointer; a non-positive size; P > H or P > W; s outside
+ *   1..S_total (pass 1, 1 for a KPCN batch without llpm); llpm without paths; use_sbmc_buf without sbmc_p. */
+int wcmc_assemble_kpcn_patches_aug(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms,
+                                   int B, int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
+                                   float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
+                                   float* target_diffuse, float* target_specular, float* target_total, void* stream);
+int wcmc_assemble_sample_patches_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
+                                     const int* origins, const int* transforms, int B, int H, int W, int S_total, int s, int P,
+                                     int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
+                                     float* target_image, void* stream);
+
 /* ---------------------------------------------------------------- full-frame evaluation
  * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
  * (scene, spp) cell.  out / ipt / tgt: fp32 (H, W, 3) images, element (y, x, c) at p[y*sh + x*sw + c*sc] (any int64

@@ -130,6 +130,8 @@ SIGNATURES = {
     "wcmc_preprocess_kpcn_prefix": (I, [P, I, I, I, I, I, I, I, P, P, Z, P]),
     "wcmc_assemble_kpcn_patches_prefix": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "wcmc_assemble_sample_patches_prefix": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "wcmc_assemble_kpcn_patches_aug": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "wcmc_assemble_sample_patches_aug": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
     "wcmc_image_eval_workspace_bytes": (Z, [I, I]),
     "wcmc_image_eval": (I, [P, L, L, L, P, L, L, L, P, L, L, L, P, L, L, L, I, I, D, P, P, Z, P]),
     "wcmc_stitch_tiles": (I, [P, L, L, L, L, I, I, P, P, I, I, I, P, I, I, I, P, P, P, P]),

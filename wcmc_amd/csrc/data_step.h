@@ -126,14 +126,40 @@ __device__ __forceinline__ int ft_mirror(int i, int n) {
   return min(max(m, 0), n - 1);
 }
 
+// value channel behind the g-th backward difference of a direction: diffuse, specular, normal (3 each), depth (1), albedo (3)
+__device__ __forceinline__ int ft_grad_src(int g) { return g < 3 ? KP_DIFF + g : g < 6 ? KP_SPEC + g - 3 : g < 9 ? KP_NORM + g - 6 :
+                                                           g < 10 ? KP_DEPTH : KP_ALB + g - 10; }
+// where that difference is stored: dx at value + 4 (depth: + 2), dy at value + 7 (depth: + 3)
+__device__ __forceinline__ int ft_grad_dst(int g, bool dy) {
+  const int src = ft_grad_src(g);
+  return src == KP_DEPTH ? src + (dy ? 3 : 2) : src + (dy ? 7 : 4);
+}
+
+// Dihedral patch transforms: code t in 0..7 is T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) on a
+// P x P window.  The map output (y, x) -> window position (sy, sx) is affine: (sy, sx) at this output pixel, and the steps
+// (xr, xc) / (yr, yc) the source takes when the output moves one pixel along x / along y.  The code is masked to 0..7 (the host
+// checks the table; the mask keeps a bad one inside the window).
+struct PatchMap { int sy, sx, xr, xc, yr, yc; };
+__device__ __forceinline__ PatchMap patch_map(int t, int y, int x, int P) {
+  const int k = t & 3, q = P - 1;
+  PatchMap m;
+  m.sy = k == 0 ? y : k == 1 ? x : k == 2 ? q - y : q - x;
+  m.sx = k == 0 ? x : k == 1 ? q - y : k == 2 ? q - x : y;
+  m.xr = k == 1 ? 1 : k == 3 ? -1 : 0;  m.xc = k == 0 ? 1 : k == 2 ? -1 : 0;
+  m.yr = k == 0 ? 1 : k == 2 ? -1 : 0;  m.yc = k == 1 ? -1 : k == 3 ? 1 : 0;
+  if (t & 4) { m.sx = q - m.sx; m.xc = -m.xc; m.yc = -m.yc; }
+  return m;
+}
+
 // Launchers of the patch-assembly kernels (preprocess.hip, sbmc_data.hip).  The per-sample buffers hold S_total samples per pixel,
-// the outputs the first s of them; the arguments have been validated by the entry point that calls.
-int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H, int W,
-                            int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+// the outputs the first s of them; the arguments have been validated by the entry point that calls.  transforms: null launches the
+// plain kernel; B device ints launch the instantiation that applies patch_map (the `_aug` entry points).
+int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms, int B,
+                            int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
                             float* specular_buffer, float* albedo, float* paths, float* target_diffuse, float* target_specular,
                             float* target_total, hipStream_t stream);
-int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins, int B,
-                       int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
-                       float* paths, float* target_image, hipStream_t stream);
+int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins,
+                       const int* transforms, int B, int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf,
+                       float* radiance, float* features, float* paths, float* target_image, hipStream_t stream);
 
 }  // namespace wcmc

@@ -15,15 +15,7 @@ struct TileOut {
   float *din, *sin, *dbuf, *sbuf, *alb, *paths;
 };
 
-// value channel behind the g-th backward difference of a direction: diffuse, specular, normal (3 each), depth (1), albedo (3)
-__device__ __forceinline__ int ft_grad_src(int g) { return g < 3 ? KP_DIFF + g : g < 6 ? KP_SPEC + g - 3 : g < 9 ? KP_NORM + g - 6 :
-                                                           g < 10 ? KP_DEPTH : KP_ALB + g - 10; }
-// where that difference is stored: dx at value + 4 (depth: + 2), dy at value + 7 (depth: + 3)
-__device__ __forceinline__ int ft_grad_dst(int g, bool dy) {
-  const int src = ft_grad_src(g);
-  return src == KP_DEPTH ? src + (dy ? 3 : 2) : src + (dy ? 7 : 4);
-}
-
+// (ft_grad_src / ft_grad_dst, the channels of the backward differences, are in data_step.h: the augmented patch assembler uses them too)
 // One thread per (tile, y, x), as pp_assemble_kpcn_kernel: every output plane is written as coalesced rows, each record is read once
 // (a second record's thirteen values only where a difference crosses the frame's edge: the outer `pad` ring of border tiles).
 template <bool VEC>

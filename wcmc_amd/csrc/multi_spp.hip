@@ -123,7 +123,7 @@ extern "C" int wcmc_assemble_kpcn_patches_prefix(const float* kpcn, const float*
   WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
                "assemble_kpcn_patches_prefix: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
   WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_prefix: llpm given without a paths output");
-  return pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, B, H, W, S_total, s, P, diffuse_in, specular_in, diffuse_buffer,
+  return pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, nullptr, B, H, W, S_total, s, P, diffuse_in, specular_in, diffuse_buffer,
                                  specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
                                  (hipStream_t)stream);
 }
@@ -138,6 +138,6 @@ extern "C" int wcmc_assemble_sample_patches_prefix(const float* sbmc_s, const fl
   WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
                "assemble_sample_patches_prefix: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
   WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_patches_prefix: llpm given without a paths output");
-  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, B, H, W, S_total, s, P, use_g_buf, use_sbmc_buf, radiance, features,
+  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, nullptr, B, H, W, S_total, s, P, use_g_buf, use_sbmc_buf, radiance, features,
                             paths, target_image, (hipStream_t)stream);
 }

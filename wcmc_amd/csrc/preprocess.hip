@@ -303,28 +303,64 @@ namespace wcmc {
 struct PatchOut {
   float *din, *sin, *dbuf, *sbuf, *alb, *paths, *tdif, *tspec, *ttot;
 };
+// AUG (the `_aug` entry point): output pixel (y, x) of patch b takes the window position patch_map gives for
+// the code transforms[b] -- the destination is untouched, only the source index is permuted, and a source is still one whole
+// 176-byte record plus its S * 148 bytes of llpm.  The backward differences are those of the transformed frame: taken again
+// from the stored value channels against the source of output (y, x - 1) / (y - 1, x) -- thirteen floats of one more record each,
+// one step outside the window at x = 0 / y = 0 -- and 0.f where that source lies outside the frame.  Where the source steps as
+// the stored difference did (+1 column for dx, +1 row for dy) the stored one is that very subtraction and is kept.
+template <bool AUG>
 __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __restrict__ kpcn, const float* __restrict__ llpm,
                                                                const float* __restrict__ gt, const int* __restrict__ origins,
-                                                               PatchOut o, int B, int H, int W, int S, int Sn, int P) {
+                                                               const int* __restrict__ transforms, PatchOut o, int B, int H, int W,
+                                                               int S, int Sn, int P) {
   // S: samples per pixel of llpm; Sn <= S: the first Sn of them go to the batch
   const int64_t total = (int64_t)B * P * P;
   const int cin = llpm ? 35 : 34;
   const int64_t plane = (int64_t)P * P;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % P), y = (int)((i / P) % P), b = (int)(i / plane);
-    const int r = origins[2 * b] + y, c = origins[2 * b + 1] + x;             // (row, column) of the image
+    PatchMap pm{y, x, 0, 1, 1, 0};
+    if (AUG) pm = patch_map(transforms[b], y, x, P);
+    const int r = origins[2 * b] + pm.sy, c = origins[2 * b + 1] + pm.sx;     // (row, column) of the image
     const int64_t pix = (int64_t)r * W + c;
     const float* k = kpcn + pix * 44;
+    float v[KP_C];                                                            // AUG: the record, its differences retaken
+    if (AUG) {
+#pragma unroll
+      for (int ch = 0; ch < KP_C; ++ch) v[ch] = k[ch];
+      if (pm.xc != 1) {
+        const int nr = r - pm.xr, nc = c - pm.xc;
+        const bool in = nr >= 0 && nr < H && nc >= 0 && nc < W;               // (clamped before use, 0 selected afterwards)
+        const float* kn = kpcn + ((int64_t)min(max(nr, 0), H - 1) * W + min(max(nc, 0), W - 1)) * KP_C;
+#pragma unroll
+        for (int g = 0; g < KP_NV; ++g) {
+          const float d = v[ft_grad_src(g)] - kn[ft_grad_src(g)];
+          v[ft_grad_dst(g, false)] = in ? d : 0.f;
+        }
+      }
+      if (pm.yr != 1) {
+        const int nr = r - pm.yr, nc = c - pm.yc;
+        const bool in = nr >= 0 && nr < H && nc >= 0 && nc < W;
+        const float* kn = kpcn + ((int64_t)min(max(nr, 0), H - 1) * W + min(max(nc, 0), W - 1)) * KP_C;
+#pragma unroll
+        for (int g = 0; g < KP_NV; ++g) {
+          const float d = v[ft_grad_src(g)] - kn[ft_grad_src(g)];
+          v[ft_grad_dst(g, true)] = in ? d : 0.f;
+        }
+      }
+    }
+    auto kv = [&](int ch) { return AUG ? v[ch] : k[ch]; };
     const int64_t po = (int64_t)y * P + x;
     float* din = o.din + (int64_t)b * cin * plane + po;
     float* sin = o.sin + (int64_t)b * cin * plane + po;
-    for (int ch = 0; ch < 10; ++ch) din[ch * plane] = k[ch];
-    for (int ch = 20; ch < 44; ++ch) din[(ch - 10) * plane] = k[ch];
-    for (int ch = 10; ch < 44; ++ch) sin[(ch - 10) * plane] = k[ch];
+    for (int ch = 0; ch < 10; ++ch) din[ch * plane] = kv(ch);
+    for (int ch = 20; ch < 44; ++ch) din[(ch - 10) * plane] = kv(ch);
+    for (int ch = 10; ch < 44; ++ch) sin[(ch - 10) * plane] = kv(ch);
     for (int ch = 0; ch < 3; ++ch) {
-      o.dbuf[((int64_t)b * 3 + ch) * plane + po] = k[ch];
-      o.sbuf[((int64_t)b * 3 + ch) * plane + po] = k[10 + ch];
-      o.alb[((int64_t)b * 3 + ch) * plane + po] = k[34 + ch] + 0.00316f;
+      o.dbuf[((int64_t)b * 3 + ch) * plane + po] = kv(ch);
+      o.sbuf[((int64_t)b * 3 + ch) * plane + po] = kv(10 + ch);
+      o.alb[((int64_t)b * 3 + ch) * plane + po] = kv(34 + ch) + 0.00316f;
     }
     if (llpm) {
       const float* l = llpm + pix * S * 37;
@@ -348,16 +384,21 @@ __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __re
   }
 }
 
-int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H, int W,
-                            int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms, int B,
+                            int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
                             float* specular_buffer, float* albedo, float* paths, float* target_diffuse, float* target_specular,
                             float* target_total, hipStream_t stream) {
   PatchOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths, target_diffuse, target_specular,
              target_total};
   const int64_t total = (int64_t)B * P * P;
   const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-  hipLaunchKernelGGL(pp_assemble_kpcn_kernel, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, o, B, H, W, S_total, s,
-                     P);
+  if (transforms) {
+    hipLaunchKernelGGL(pp_assemble_kpcn_kernel<true>, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, transforms, o, B, H, W,
+                       S_total, s, P);
+    return check_launch("assemble_kpcn_patches_aug");
+  }
+  hipLaunchKernelGGL(pp_assemble_kpcn_kernel<false>, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, transforms, o, B, H, W,
+                     S_total, s, P);
   return check_launch("assemble_kpcn_patches");
 }
 }  // namespace wcmc
@@ -371,7 +412,26 @@ extern "C" int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, 
                    specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse && target_specular &&
                    target_total && (!llpm || (paths && S > 0)),
                WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: bad argument");
-  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, B, H, W, S, S, P, diffuse_in, specular_in, diffuse_buffer,
+  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, nullptr, B, H, W, S, S, P, diffuse_in, specular_in, diffuse_buffer,
                                        specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
+                                       (hipStream_t)stream);
+}
+
+extern "C" int wcmc_assemble_kpcn_patches_aug(const float* kpcn, const float* llpm, const float* gt, const int* origins,
+                                              const int* transforms, int B, int H, int W, int S_total, int s, int P,
+                                              float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer,
+                                              float* albedo, float* paths, float* target_diffuse, float* target_specular,
+                                              float* target_total, void* stream) {
+  WCMC_REQUIRE(transforms, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: null transforms (one code 0..7 per patch)");
+  WCMC_REQUIRE(kpcn && gt && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse &&
+                   target_specular && target_total,
+               WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: null pointer");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: B, H, W, P must be positive");
+  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: a %d-pixel patch does not fit the %d x %d frame", P, H, W);
+  WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_patches_aug: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: llpm given without a paths output");
+  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, transforms, B, H, W, S_total, s, P, diffuse_in, specular_in,
+                                       diffuse_buffer, specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
                                        (hipStream_t)stream);
 }

@@ -101,8 +101,14 @@ __device__ __forceinline__ float* sa_dst(const SampleBatch& a, int k, int b, int
   return a.tgt + ((int64_t)b * 3 + ch) * plane;
 }
 
-__global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const int* __restrict__ origins, int64_t units, int B,
-                                                          int H, int W, int S, int P) {
+// AUG (the `_aug` entry point): the unit's 32 output pixels (y, x0 + px) take the window positions patch_map
+// gives for the code transforms[b].  The map is affine, so the 32 source runs are `step` floats apart -- one pixel pitch forwards
+// or backwards along a source row, or a whole source row up or down for the transposing codes -- instead of one pitch; every
+// channel is a copy, and the LDS tile and the writes are the plain form's.
+template <bool AUG>
+__global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const int* __restrict__ origins,
+                                                          const int* __restrict__ transforms, int64_t units, int B, int H, int W,
+                                                          int S, int P) {
   extern __shared__ __attribute__((aligned(16))) float sa_tile[];
   const int nxc = (P + SA_XT - 1) / SA_XT;
   const int64_t plane = (int64_t)P * P;
@@ -118,13 +124,23 @@ __global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const i
     const int x0 = xc * SA_XT, xcnt = min(SA_XT, P - x0);
     const int s0 = sc * SA_SC, scnt = min(SA_SC, sr.S - s0);
     // (the host checks the origins; the clamp keeps a bad one from reading outside the image)
-    const int r = min(max(origins[2 * b], 0), H - P) + y, c = min(max(origins[2 * b + 1], 0), W - P) + x0;
+    PatchMap pm{y, x0, 0, 1, 1, 0};
+    if (AUG) pm = patch_map(transforms[b], y, x0, P);
+    const int r = min(max(origins[2 * b], 0), H - P) + pm.sy, c = min(max(origins[2 * b + 1], 0), W - P) + pm.sx;
     const int run = scnt * sr.C, LD = (SA_SC * sr.C) | 1;
     const int64_t pitch = (int64_t)sr.Sp * sr.C;
     const float* base = sr.p + ((int64_t)r * W + c) * pitch + (int64_t)s0 * sr.C;
-    for (int f = threadIdx.x; f < xcnt * run; f += 256) {
-      const int px = f / run, e = f - px * run;
-      sa_tile[px * LD + e] = base[px * pitch + e];
+    if (AUG) {
+      const int64_t step = ((int64_t)pm.xr * W + pm.xc) * pitch;             // from the source of (y, x) to that of (y, x + 1)
+      for (int f = threadIdx.x; f < xcnt * run; f += 256) {
+        const int px = f / run, e = f - px * run;
+        sa_tile[px * LD + e] = base[px * step + e];
+      }
+    } else {
+      for (int f = threadIdx.x; f < xcnt * run; f += 256) {
+        const int px = f / run, e = f - px * run;
+        sa_tile[px * LD + e] = base[px * pitch + e];
+      }
     }
     __syncthreads();
     const int rows = scnt * sr.nout;
@@ -144,9 +160,9 @@ static unsigned sb_grid(int64_t work) {
   return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins, int B,
-                       int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
-                       float* paths, float* target_image, hipStream_t stream) {
+int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins,
+                       const int* transforms, int B, int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf,
+                       float* radiance, float* features, float* paths, float* target_image, hipStream_t stream) {
   SampleBatch a;
   a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = target_image;
   a.ng = use_g_buf ? 24 : 3;
@@ -162,8 +178,13 @@ int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* ll
     if (a.src[k].nout > 0) units += rows * ((a.src[k].S + SA_SC - 1) / SA_SC);
   }
   const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  hipLaunchKernelGGL(sa_assemble_kernel, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins, units,
-                     B, H, W, s, P);
+  if (transforms) {
+    hipLaunchKernelGGL(sa_assemble_kernel<true>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins,
+                       transforms, units, B, H, W, s, P);
+    return check_launch("assemble_sample_patches_aug");
+  }
+  hipLaunchKernelGGL(sa_assemble_kernel<false>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins,
+                     transforms, units, B, H, W, s, P);
   return check_launch("assemble_sample_patches");
 }
 
@@ -281,6 +302,24 @@ extern "C" int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sb
   WCMC_REQUIRE(sbmc_s && gt && origins && B > 0 && H > 0 && W > 0 && S > 0 && P > 0 && P <= H && P <= W && radiance &&
                    features && target_image && (!use_sbmc_buf || sbmc_p) && (!llpm || paths),
                WCMC_ERR_BAD_ARG, "assemble_sample_patches: bad argument");
-  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, B, H, W, S, S, P, use_g_buf, use_sbmc_buf, radiance, features, paths,
-                            target_image, (hipStream_t)stream);
+  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, nullptr, B, H, W, S, S, P, use_g_buf, use_sbmc_buf, radiance, features,
+                            paths, target_image, (hipStream_t)stream);
+}
+
+extern "C" int wcmc_assemble_sample_patches_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
+                                                const int* origins, const int* transforms, int B, int H, int W, int S_total, int s,
+                                                int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
+                                                float* target_image, void* stream) {
+  WCMC_REQUIRE(transforms, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: null transforms (one code 0..7 per patch)");
+  WCMC_REQUIRE(sbmc_s && gt && origins && radiance && features && target_image, WCMC_ERR_BAD_ARG,
+               "assemble_sample_patches_aug: null pointer");
+  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: use_sbmc_buf needs sbmc_p");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: B, H, W, P must be positive");
+  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: a %d-pixel patch does not fit the %d x %d frame", P, H,
+               W);
+  WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
+               "assemble_sample_patches_aug: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: llpm given without a paths output");
+  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, transforms, B, H, W, S_total, s, P, use_g_buf, use_sbmc_buf, radiance,
+                            features, paths, target_image, (hipStream_t)stream);
 }

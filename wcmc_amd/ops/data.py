@@ -137,10 +137,44 @@ def _need_origins(who, origins):
     assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
 
 
-def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
+def check_patch_transforms(transforms, b, who="assemble_kpcn_patches"):
+    """Host check of a table of patch transform codes: ``b`` int32 codes in 0..7, one per patch, as a 1-D
+    tensor or array.  The codes are data, as origins are: a device tensor is read back here (which synchronises), so a caller that
+    assembles many batches from one table checks it once and passes ``check_transforms=False``."""
+    import numpy as np
+    if isinstance(transforms, torch.Tensor):
+        if transforms.dtype != torch.int32:
+            raise ValueError("%s: transforms should be int32, got %s" % (who, transforms.dtype))
+        t = transforms.detach().cpu().numpy()
+    else:
+        t = np.asarray(transforms)
+        if t.dtype != np.int32:
+            raise ValueError("%s: transforms should be int32, got %s" % (who, t.dtype))
+    if t.ndim != 1 or t.shape[0] != int(b):
+        raise ValueError("%s: transforms should hold one code per patch, shape (%d,), got %s" % (who, int(b), tuple(t.shape)))
+    if t.size and (int(t.min()) < 0 or int(t.max()) > 7):
+        raise ValueError("%s: a transform code lies outside 0..7 (got %d..%d)" % (who, int(t.min()), int(t.max())))
+
+
+def _transforms_dev(who, transforms, b, device, check):
+    """The (b,) int32 device table the `_aug` kernels read.  ``check=False`` still refuses a wrong dtype or length (no read-back)."""
+    if check:
+        check_patch_transforms(transforms, b, who)
+    if not isinstance(transforms, torch.Tensor):
+        import numpy as np
+        transforms = torch.from_numpy(np.ascontiguousarray(transforms))
+    if transforms.dtype != torch.int32 or transforms.dim() != 1 or transforms.shape[0] != b:
+        raise ValueError("%s: transforms should be (%d,) int32, got %s %s" % (who, b, tuple(transforms.shape), transforms.dtype))
+    return transforms.to(device).contiguous()
+
+
+def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None, transforms=None, check_transforms=True):
     """The batch dictionary of the KPCN base model for windows of `patch` pixels at `origins` ((B, 2) int32 device
     tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device).  ``spp``: the batch takes
-    the first ``spp`` of llpm's samples (``wcmc_assemble_kpcn_patches_prefix``; ``kpcn`` is then that count's buffer); None: all."""
+    the first ``spp`` of llpm's samples (``wcmc_assemble_kpcn_patches_prefix``; ``kpcn`` is then that count's buffer); None: all.
+    ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array; ``wcmc_assemble_kpcn_patches_aug``,
+    DESIGN.md section 20): entry b is ``rot90(fliplr(w) if t & 4 else w, t & 3)`` of its window w as if the whole frame had been
+    transformed before preprocessing -- per-pixel channels copied, the backward differences retaken along the new axes."""
     _need_cuda(kpcn, gt)
     _need_origins("assemble_kpcn_patches", origins)
     h, w = kpcn.shape[:2]
@@ -164,7 +198,11 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None):
             _ptr(out["kpcn_specular_buffer"]), _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
             _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream())
     ins = (_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
-    if spp is not None and llpm is not None:
+    if transforms is not None:                        # (without llpm no sample is read: the entry point still wants 1 <= s <= S_total)
+        tr = _transforms_dev("assemble_kpcn_patches", transforms, b, kpcn.device, check_transforms)
+        check(lib().wcmc_assemble_kpcn_patches_aug(*ins[:4], ctypes.c_void_p(tr.data_ptr()), b, h, w, max(s_total, 1), max(s, 1),
+                                                   patch, *outs), "assemble_kpcn_patches_aug")
+    elif spp is not None and llpm is not None:
         check(lib().wcmc_assemble_kpcn_patches_prefix(*ins, s_total, s, patch, *outs), "assemble_kpcn_patches_prefix")
     else:                                             # (without llpm nothing in the batch depends on the sample count)
         check(lib().wcmc_assemble_kpcn_patches(*ins, s, patch, *outs), "assemble_kpcn_patches")
@@ -217,13 +255,17 @@ def _check_sample_buffers(who, sbmc_p, llpm, h, w, s):
 
 
 def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True,
-                            spp=None):
+                            spp=None, transforms=None):
     """The batch dictionary of the SBMC / LBMC interfaces (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and
     ``target_image``) for windows of ``patch`` pixels at ``origins`` ((B, 2) int32 (row, column); numpy or tensor) of one image's
     buffers (datasets.py:1045-1073, 1086-1118 and ``_transpose`` on the device, one launch).  ``sbmc_p`` may be None without
     ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  ``check_origins=False``: the caller has checked them
     on the host (checking a device tensor here synchronises).  ``spp``: the batch takes the first ``spp`` samples of the buffers
-    (``wcmc_assemble_sample_patches_prefix``: the buffers are per-sample, so the prefix is a slice); None: all of them."""
+    (``wcmc_assemble_sample_patches_prefix``: the buffers are per-sample, so the prefix is a slice); None: all of them.
+    ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array; ``wcmc_assemble_sample_patches_aug``,
+    DESIGN.md section 20): every entry of patch b is ``rot90(fliplr(w) if t & 4 else w, t & 3)`` of its window w on the two pixel
+    axes -- all channels are per sample, so all are copies (subpixel and light directions included: not re-expressed).  The table is
+    checked on the host together with the origins (``check_origins``)."""
     _need_cuda(sbmc_s, gt)
     h, w, s = sbmc_s.shape[:3]
     if tuple(sbmc_s.shape) != (h, w, s, 27) or tuple(gt.shape) != (h, w, 9) or not (sbmc_s.is_contiguous() and gt.is_contiguous()):
@@ -254,7 +296,11 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
     ins = (_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
     outs = (patch, int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
             _ptr(out.get("paths")), _ptr(out["target_image"]), _stream())
-    if spp is not None:
+    if transforms is not None:
+        tr = _transforms_dev("assemble_sample_patches", transforms, b, sbmc_s.device, check_origins)
+        check(lib().wcmc_assemble_sample_patches_aug(*ins[:5], ctypes.c_void_p(tr.data_ptr()), b, h, w, s_total, s, *outs),
+              "assemble_sample_patches_aug")
+    elif spp is not None:
         check(lib().wcmc_assemble_sample_patches_prefix(*ins, s_total, s, *outs), "assemble_sample_patches_prefix")
     else:
         check(lib().wcmc_assemble_sample_patches(*ins, s, *outs), "assemble_sample_patches")

@@ -77,10 +77,11 @@ class SamplePatchBatcher:
     def check_origins(self, origins, h, w):
         _ops.check_patch_origins(origins, h, w, self.patch_size, who="SamplePatchBatcher")
 
-    def batch(self, sbmc_s, sbmc_p, llpm, gt, origins, check=True, spp=None):
-        """``spp``: the first ``spp`` samples of the buffers (datasets.py:1053-1054, 1091); None: all of them."""
+    def batch(self, sbmc_s, sbmc_p, llpm, gt, origins, check=True, spp=None, transforms=None):
+        """``spp``: the first ``spp`` samples of the buffers (datasets.py:1053-1054, 1091); None: all of them.  ``transforms``: one
+        dihedral code 0..7 per patch (``ops.check_patch_transforms``; checked with the origins) or None."""
         return _ops.assemble_sample_patches(sbmc_s, sbmc_p if self.use_sbmc_buf else None, llpm, gt, origins, self.patch_size,
-                                            self.use_g_buf, self.use_sbmc_buf, check_origins=check, spp=spp)
+                                            self.use_g_buf, self.use_sbmc_buf, check_origins=check, spp=spp, transforms=transforms)
 
 
 class PatchBatcher:
@@ -111,15 +112,17 @@ class PatchBatcher:
         """Windows must lie inside the image (the reference would silently return a smaller patch)."""
         _ops.check_patch_origins(origins, h, w, self.patch_size, who="PatchBatcher")
 
-    def batch(self, kpcn, llpm, gt, origins, check=True, spp=None):
+    def batch(self, kpcn, llpm, gt, origins, check=True, spp=None, transforms=None):
         """kpcn (H,W,44), llpm (H,W,S,37) or None, gt (H,W,9): device tensors; origins: (B,2) rows/columns (numpy or
         tensor).  ``check=False``: the caller has run ``check_origins`` on them (``PatchLoader`` does, once per image, on the
         host copy -- checking a device tensor here would synchronise every batch).  ``spp``: ``kpcn`` is the buffer of the first
-        ``spp`` samples and the batch takes that prefix of ``llpm`` (datasets.py:1091); None: all of its samples."""
+        ``spp`` samples and the batch takes that prefix of ``llpm`` (datasets.py:1091); None: all of its samples.  ``transforms``: one
+        dihedral code 0..7 per patch (``ops.check_patch_transforms``; ``check`` covers it too) or None."""
         if check:
             self.check_origins(origins, *kpcn.shape[:2])
         o = torch.as_tensor(np.asarray(origins), dtype=torch.int32) if not isinstance(origins, torch.Tensor) else origins
-        return _ops.assemble_kpcn_patches(kpcn, llpm, gt, o.to(kpcn.device, torch.int32).contiguous(), self.patch_size, spp=spp)
+        return _ops.assemble_kpcn_patches(kpcn, llpm, gt, o.to(kpcn.device, torch.int32).contiguous(), self.patch_size, spp=spp,
+                                          transforms=transforms, check_transforms=check)
 
 
 SamplePatchBatcher.sample_origins = PatchBatcher.sample_origins

@@ -31,6 +31,7 @@ import threading
 import numpy as np
 import torch
 
+from .. import ops as _ops
 from .datasets import DenoisePreprocessor, PatchBatcher, SamplePatchBatcher, check_counts, sample_flags
 
 
@@ -237,12 +238,22 @@ class PatchLoader:
     ``multi_count_schedule(len(indices), counts, window)``; every ``(image, count)`` gets ``patches_per_image`` patches at fresh
     origins (the reference draws them per dataset, i.e. per count: ``datasets.py:795-810``) assembled from the first ``count``
     samples of the image's buffers, so every batch has one sample count.  Up to ``window`` staged images stay resident;
-    ``report`` (e.g. ``print``) is told their footprint once."""
+    ``report`` (e.g. ``print``) is told their footprint once.
+
+    ``augment``: every patch is assembled under one of the eight dihedral transforms of the square, drawn
+    uniformly -- the distribution of the reference's ``_random_rot(_random_flip(.))`` (datasets.py:718-758).  The codes come from
+    ``patch_transforms``: a generator of their own, keyed by ``augment_seed``, the pass, the image's index in the dataset and the
+    sample count -- never the process-wide ``np.random``, so the origins are those of ``augment=False``, and never the rank, so a
+    given image gets the same codes however the images are sharded.  One upload per image, beside the origins'."""
 
     def __init__(self, reader, indices, device, batch_size=8, patch_size=PatchBatcher.PATCH_SIZE, use_llpm=True, depth=2,
                  patches_per_image=None, prefetch=2, workers=2, staged_hook=None, base_model='kpcn', use_g_buf=True,
-                 use_sbmc_buf=True, counts=None, window=1, report=None):
+                 use_sbmc_buf=True, counts=None, window=1, report=None, augment=False, augment_seed=0):
         base_model, use_g_buf, use_sbmc_buf = sample_flags(base_model, use_g_buf, use_sbmc_buf)
+        self.augment, self.augment_seed = bool(augment), int(augment_seed)
+        if self.augment_seed < 0:
+            raise ValueError("PatchLoader: augment_seed must be non-negative, got %d" % self.augment_seed)
+        self.epoch = -1                                               # passes begun so far - 1: `__iter__` counts them
         self.stager = ImageStager(reader, indices, device, depth=depth, use_llpm=use_llpm, workers=workers,
                                   staged_hook=staged_hook, base_model=base_model, counts=counts)
         self.counts, self.window, self.report = self.stager.counts, max(1, int(window)), report
@@ -293,20 +304,35 @@ class PatchLoader:
         self.batcher.check_origins(origins, h, w)
         return origins
 
-    def _assemble(self, bufs, origins, out_q, stop, spp=None):
-        """Enqueue the assembly of one image's batches on the side stream and hand them over; False: the consumer has gone."""
+    def patch_transforms(self, image, n=None, epoch=None, spp=None):
+        """The dihedral codes (int32, 0..7) of the ``n`` patches (default: ``patches_per_image``) drawn from dataset image ``image`` in
+        pass ``epoch`` (default: the current one; the first pass is 0) at sample count ``spp`` (None without ``counts``), in the order
+        of the image's origins.  A pure function of ``(augment_seed, epoch, image, spp)``: it touches no shared random state."""
+        n = self.batcher.patches_per_image if n is None else int(n)
+        epoch = max(self.epoch, 0) if epoch is None else int(epoch)
+        rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.augment_seed, epoch, int(image), int(spp or 0)])))
+        return rng.integers(0, 8, size=n, dtype=np.int32)
+
+    def _assemble(self, bufs, origins, out_q, stop, spp=None, image=None):
+        """Enqueue the assembly of one image's batches on the side stream and hand them over; False: the consumer has gone.
+        ``image``: its index in the dataset (what keys the transform codes under ``augment``)."""
         side = self.assemble_stream
         with torch.cuda.stream(side):
             origins_dev = torch.as_tensor(origins, dtype=torch.int32).to(self.stager.device)      # one copy per image
+            kw = {} if spp is None else {'spp': spp}
+            codes_dev = None
+            if self.augment:
+                codes = self.patch_transforms(image, len(origins), spp=spp)
+                _ops.check_patch_transforms(codes, len(origins), who="PatchLoader")               # on the host copy, once per image
+                codes_dev = torch.from_numpy(codes).to(self.stager.device)                        # one copy per image
             for k in range(0, len(origins), self.batch_size):
                 if self._paced and not self._tick.acquire(timeout=self.pace_timeout):
                     self._paced = False           # no kick within the timeout: this consumer does not pace -- stop waiting for it
                 if stop.is_set():
                     return False
-                if spp is None:
-                    batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False)
-                else:
-                    batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False, spp=spp)
+                if codes_dev is not None:
+                    kw['transforms'] = codes_dev[k:k + self.batch_size]
+                batch = self.batcher.batch(*bufs, origins_dev[k:k + self.batch_size], check=False, **kw)
                 ev = torch.cuda.Event()
                 ev.record(side)
                 if not ImageStager._put(out_q, (batch, ev), stop):
@@ -343,7 +369,7 @@ class PatchLoader:
             origins = self._origins(prob, h, w)
             if self.kpcn_slabs:
                 bufs[0] = bufs[0][s - self.counts[0]]
-            if not self._assemble(bufs, origins, out_q, stop, spp=s):
+            if not self._assemble(bufs, origins, out_q, stop, spp=s, image=self.stager.indices[i]):
                 return False
         return True
 
@@ -358,6 +384,7 @@ class PatchLoader:
             images = iter(self.stager)
             if self.counts is not None and not self._produce_counts(images, out_q, stop):
                 return
+            position = 0                                          # of the image in `indices`
             while self.counts is None and not stop.is_set():
                 with torch.cuda.stream(side):                     # (the stager hands its buffers to the CURRENT stream)
                     got = next(images, None)
@@ -365,8 +392,9 @@ class PatchLoader:
                     break
                 *bufs, prob = got                                 # (kpcn | sbmc_s, sbmc_p), llpm, gt
                 h, w = bufs[0].shape[:2]
-                if not self._assemble(bufs, self._origins(prob, h, w), out_q, stop):
+                if not self._assemble(bufs, self._origins(prob, h, w), out_q, stop, image=self.stager.indices[position]):
                     return
+                position += 1
             ImageStager._put(out_q, None, stop)
         except BaseException as exc:                              # surface reader / CUDA errors in the consumer
             ImageStager._put(out_q, exc, stop)
@@ -387,6 +415,7 @@ class PatchLoader:
         self._paced = False
         while self._tick.acquire(blocking=False):
             pass
+        self.epoch += 1                                           # (keys the transform codes of this pass: patch_transforms)
         worker = threading.Thread(target=self._produce, args=(out_q, stop), daemon=True)
         worker.start()
         try:

@@ -191,6 +191,13 @@ def multi_spp_loader_args(args, rank=0):
     return dict(counts=counts, window=args.ms_window, report=print if rank == 0 else None), counts
 
 
+def augment_loader_args(args):
+    """``augment`` / ``augment_seed`` of the TRAINING ``PatchLoader`` under ``--augment`` (else empty); validation never augments."""
+    if not getattr(args, 'augment', False):
+        return {}
+    return dict(augment=True, augment_seed=getattr(args, 'augment_seed', None) or 0)
+
+
 def init_data_dir(args, device, rank=0, world=1):
     """``--from_data_dir``: ``<data_dir>/train`` through the patch loader, ``<data_dir>/val`` on the grid of ``_full_patches``
     (``train_kpcn.py:167-189``).  Image indices are strided by rank; every rank gets the same number of images (the ranks step
@@ -207,7 +214,7 @@ def init_data_dir(args, device, rank=0, world=1):
     ms, counts = multi_spp_loader_args(args, rank)
     train = PatchLoader(tr.reader, shard(tr), device, batch_size=args.batch_size, patch_size=args.patch_size,
                         use_llpm=args.use_llpm_buf, patches_per_image=getattr(args, 'patches_per_image', None),
-                        staged_hook=tr.staged_hook, **ms)
+                        staged_hook=tr.staged_hook, **ms, **augment_loader_args(args))
     val = GridValLoader(va, shard(va), BS_VAL, counts=counts)
     sizes = {'dncnn_in_size': tr.dncnn_in_size, 'pnet_in_size': PNET_IN, 'pnet_out_size': tr.pnet_out_size}
     return sizes, {'train': train, 'val': val}
@@ -386,11 +393,14 @@ MS_WINDOW = 8       # default of --ms_window (0.5 s per ca
 
 MULTI_SPP_EPILOG = ('additions of this build, on train_kpcn, train_sbmc and train_lbmc alike: --multi_spp (with --from_data_dir: train '
                     'and validate at every sample count 2..--num_samples) and --ms_window K (images kept on the device while the '
-                    'counts are walked over them; default %d)' % MS_WINDOW)
+                    'counts are walked over them; default %d); --augment (with --from_data_dir: every training patch under one of '
+                    'the eight flips / quarter turns of the square, drawn uniformly; validation is never augmented) and '
+                    '--augment_seed N (seed of that draw, a random stream of its own; default 0)' % MS_WINDOW)
 
 
 def multi_spp_parser():
-    """``--multi_spp`` / ``--ms_window``: additions of this build (the reference always trains over 2..spp, ``train_kpcn.py:170-173``).
+    """``--multi_spp`` / ``--ms_window`` (the reference always trains over 2..spp, ``train_kpcn.py:170-173``) and ``--augment`` /
+    ``--augment_seed``: additions of this build.
     A parser of their own, read before the launcher's: ``build_parser()`` of each launcher stays the reference's flag surface plus
     what earlier rounds added, which tests pin flag by flag."""
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
@@ -401,6 +411,13 @@ def multi_spp_parser():
                    help='an addition of this build; with --multi_spp: images whose buffers stay on the device while the counts are '
                         'walked over them -- all counts of K images, then the next K.  K >= the number of training images is the '
                         "reference's order; with --graph there is one capture per (window, count)")
+    p.add_argument('--augment', action='store_true',
+                   help='an addition of this build; with --from_data_dir: every training patch under one of the eight flips / '
+                        "quarter turns of the square, drawn uniformly (the reference's _random_rot(_random_flip(.)), which it leaves "
+                        'switched off), gradients retaken along the new axes; validation is never augmented')
+    p.add_argument('--augment_seed', type=int, default=None, metavar='N',
+                   help='an addition of this build; with --augment: seed of the transform draw, a random stream of its own '
+                        '(default 0); the patch origins do not depend on it')
     return p
 
 
@@ -424,9 +441,26 @@ def check_multi_spp_args(args):
             raise RuntimeError('spp too low to randomize sample count')                  # datasets.py:1158-1160
 
 
+def check_augment_args(args):
+    """``--augment`` / ``--augment_seed`` act on the patch loader of a dataset directory only; ``augment_seed`` None -> 0."""
+    if getattr(args, 'augment', False) and not getattr(args, 'from_data_dir', False):
+        raise RuntimeError('`--augment` transforms the patches the loader of a dataset directory assembles: it needs `--from_data_dir`')
+    if getattr(args, 'augment_seed', None) is not None:
+        if not getattr(args, 'from_data_dir', False):
+            raise RuntimeError('`--augment_seed` seeds the transform draw of the loader of a dataset directory: it needs '
+                               '`--from_data_dir`')
+        if not getattr(args, 'augment', False):
+            raise RuntimeError('`--augment_seed` needs `--augment`')
+        if args.augment_seed < 0:
+            raise RuntimeError('`--augment_seed` should be non-negative')
+    elif hasattr(args, 'augment_seed'):
+        args.augment_seed = 0
+
+
 def check_args(args):
     """The argument errors of ``train_kpcn.py:427-441``."""
     check_multi_spp_args(args)
+    check_augment_args(args)
     if args.manif_learn and not args.use_llpm_buf:
         raise RuntimeError('The manifold learning module requires a llpm-specific buffer.')
     if args.manif_learn and not args.manif_loss:

@@ -78,7 +78,8 @@ def init_data(args, device, base_model='sbmc', use_sbmc_buf=None):
     ms, counts = tk.multi_spp_loader_args(args)
     train = PatchLoader(tr.reader, range(len(tr)), device, batch_size=args.batch_size, patch_size=args.patch_size,
                         use_llpm=args.use_llpm_buf, patches_per_image=args.patches_per_image, staged_hook=tr.staged_hook,
-                        base_model=tr.base_model, use_g_buf=tr.use_g_buf, use_sbmc_buf=tr.use_sbmc_buf, **ms)
+                        base_model=tr.base_model, use_g_buf=tr.use_g_buf, use_sbmc_buf=tr.use_sbmc_buf, **ms,
+                        **tk.augment_loader_args(args))
     val = tk.GridValLoader(va, range(len(va)), BS_VAL, counts=counts)
     sizes = {'dncnn_in_size': tr.dncnn_in_size, 'pnet_in_size': tr.pnet_in_size, 'pnet_out_size': tr.pnet_out_size}
     return sizes, {'train': train, 'val': val}
