@@ -257,6 +257,22 @@ int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int p
                     const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
                     const void* wt1, const float* gout, float* dy, float* dprop, float* dw0, float* db0, float* dw1,
                     float* db1, void* workspace, size_t workspace_bytes, void* stream);
+/* The same pair with h's hi plane and out handed from the forward to the backward instead of recomputed.  All the backward uses
+ * of the hidden activation is its bf16 hi plane (ReLU gate, one-term dW1), all it uses of out is its sign:
+ *   wcmc_final2_fwd_save   wcmc_final2_fwd that also writes h_hi, a dense bf16 plane [M][128] (256 B per pixel); out is bit for
+ *                          bit wcmc_final2_fwd's.
+ *   wcmc_final2_bwd_saved  wcmc_final2_bwd on that h_hi and on out as the forward wrote it (read only): no recomputation (58
+ *                          instead of 118 MFMAs per 64-pixel tile and wave), all eight results bit for bit wcmc_final2_bwd's.
+ * Errors before any launch, after those of wcmc_final2_fwd / _bwd's own arguments: a null h_hi / out WCMC_ERR_BAD_ARG, one
+ * that is not 16-byte aligned WCMC_ERR_ALIGNMENT (the output of the forward: WCMC_ERR_BAD_ARG, as in wcmc_final2_fwd), then a
+ * short workspace WCMC_ERR_WORKSPACE (wcmc_final2_bwd_workspace_bytes() serves both backwards). */
+int wcmc_final2_fwd_save(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                         const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
+                         void* stream);
+int wcmc_final2_bwd_saved(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                          const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
+                          const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
+                          float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream);
 size_t wcmc_conv2d_igemm_colsum_elems(int N, int Ho, int Wo, int Cout);
 int wcmc_colsum_finish(const float* partial, int N, int Ho, int Wo, int Cout, float* db, void* stream);
 /* Which kernel a launch WOULD run, from the code that launches, without touching the device (no GPU needed).  Each writes two

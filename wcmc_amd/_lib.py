@@ -92,6 +92,8 @@ SIGNATURES = {
     "wcmc_final2_bwd_workspace_bytes": (Z, []),
     "wcmc_final2_fwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P]),
     "wcmc_final2_bwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, Z, P]),
+    "wcmc_final2_fwd_save": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P]),
+    "wcmc_final2_bwd_saved": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, Z, P]),
     "wcmc_embed3_supported": (I, [I, I, I, I]),
     "wcmc_embed3_bwd_workspace_bytes": (Z, []),
     "wcmc_embed3_fwd": (I, [P, L, I, P, P, P, P, P, P, P, P]),

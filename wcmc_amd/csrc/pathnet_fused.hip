@@ -469,8 +469,10 @@ __global__ __launch_bounds__(256) void embed3_bwd_finish_kernel(const float* __r
 // gradient (537 MB fp32) only to slice it into d_y and sum the other half over the samples.  Here a workgroup (eight
 // waves, one cout tile of the 128 each) owns "super-tiles": 64 pixels of one image x its S samples.  prop's 64 pixels
 // are split into the tile once per super-tile; per sample the y tile arrives, the concatenation and the hidden
-// activation live in LDS only; the backward recomputes them, gates with them, writes d_y, keeps d_prop in registers over
-// the S samples (written once) and accumulates all weight / bias gradients in registers across the workgroup's tiles.
+// activation live in LDS only; the backward recomputes them (wcmc_final2_bwd) or reads what it needs of them -- h's hi plane, out's
+// sign -- from a forward that wrote them (wcmc_final2_fwd_save / _bwd_saved: f2_bwd_saved below), gates with them, writes d_y, keeps
+// d_prop in registers over the S samples (written once) and accumulates all weight / bias gradients in registers across the
+// workgroup's tiles.
 constexpr int F2_C = 128;                  // concatenation and hidden width
 constexpr int F2_RS = 144;                 // LDS row stride in bf16: 288 B = 9 x 32 (conflict-free transposing reads)
 constexpr int F2_TILE = E3_TP * F2_RS;
@@ -484,6 +486,7 @@ struct F2Params {
   const u16* wp0; const u16* wp1;          // forward packs: [128][2][128], [16][2][128]
   const float* b0; const float* b1; int outc;
   float* out; int os;                      // fp32 [M][os], os = round_up(outc, 4) = 4 or 8
+  u16* hsave; unsigned h_bytes;            // optional: the hi plane of h, dense bf16 [M][128] (forward writes it, the saved backward reads it and out)
   // backward
   const u16* wt0; const u16* wt1;          // data-gradient packs: [128][2][128] (rows = concat channels), [128][2][32] (rows = hidden channels)
   const float* gout;                       // fp32 [M][os]
@@ -577,8 +580,82 @@ __device__ __forceinline__ void f2_store_relu_split(const f32x4 (&acc)[4], const
   }
 }
 
+// the hi plane alone (the saved backward multiplies nothing by a lo plane): the same bits f2_store64_split puts into th
+__device__ __forceinline__ void f2_store64_hi(const F2Pre& o, u16* th, int c0, int tid) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = tid + 512 * k, px = v >> 4, c4 = (v & 15) * 4;
+    u16 hi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hi[e] = e3_bf(e3_u2f(o.v[k][e]));
+    *reinterpret_cast<u32x2*>(th + px * F2_RS + c0 + c4) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+  }
+}
+// h's hi plane between its LDS tile [64][F2_RS] and the dense bf16 plane [M][128]: whole 256-byte rows, two 16-byte units per
+// thread of 512 (unit v = tid + 512 k: pixel v >> 4, channels 8 (v & 15) ..)
+__device__ __forceinline__ void f2_save_h(const u16* th, const __amdgpu_buffer_rsrc_t r, int64_t m0, int tid) {
+  const unsigned base = (unsigned)(m0 * 256);                  // (m0 is wave-uniform; M * 256 < 2 GiB: checked by the host)
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = tid + 512 * k, px = v >> 4, u = v & 15;
+    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(th + px * F2_RS + u * 8), r, base + (unsigned)(px * 256 + u * 16), 0, 0);
+  }
+}
+__device__ __forceinline__ F2Pre f2_load_h(const __amdgpu_buffer_rsrc_t r, int64_t m0, int tid) {
+  F2Pre o;
+  const unsigned base = (unsigned)(m0 * 256);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = tid + 512 * k, px = v >> 4, u = v & 15;
+    o.v[k] = __builtin_amdgcn_raw_buffer_load_b128(r, base + (unsigned)(px * 256 + u * 16), 0, 0);
+  }
+  return o;
+}
+__device__ __forceinline__ void f2_store_h(const F2Pre& o, u16* th, int tid) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = tid + 512 * k, px = v >> 4, u = v & 15;
+    *reinterpret_cast<u32x4*>(th + px * F2_RS + u * 8) = o.v[k];
+  }
+}
+
+// The per-workgroup partials of a backward: dW0 [128][128] | dW1 [16][128] | db0 [128] | db1 [16] (red: [16][128] + [64][8] floats of LDS)
+__device__ __forceinline__ void f2_bwd_partials(float* ws, float* redb, const f32x4 (&gw0)[8], const f32x4& gw1, const float (&sb0)[4],
+                                                const float (&sb1)[4], int tid) {
+  const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, q = lane >> 4;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ws[(16 * wave + 4 * q + e) * F2_C + 16 * j + fr] = gw0[j][e];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ws[F2_C * F2_C + (4 * q + e) * F2_C + 16 * wave + fr] = gw1[e];
+  __syncthreads();
+  // redb: [16 pixel columns][128 channels], then [64 threads][8]
+#pragma unroll
+  for (int e = 0; e < 4; ++e) redb[fr * F2_C + 16 * wave + 4 * q + e] = sb0[e];
+  if (wave < 4 && q < 2) {                                       // (lanes q = 1 hold zeros when os == 4)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) redb[16 * F2_C + (16 * wave + fr) * 8 + 4 * q + e] = sb1[e];
+  }
+  __syncthreads();
+  if (tid < F2_C) {
+    float sacc = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc += redb[r * F2_C + tid];
+    ws[F2_C * F2_C + 16 * F2_C + tid] = sacc;
+  } else if (tid < F2_C + 16) {
+    const int c = tid - F2_C;
+    float sacc = 0.f;
+    if (c < 8)
+      for (int r = 0; r < 64; ++r) sacc += redb[16 * F2_C + r * 8 + c];
+    ws[F2_C * F2_C + 16 * F2_C + F2_C + c] = sacc;
+  }
+}
+
+// The chain as the forward computes it.  BWD: the backward that RECOMPUTES c's lo plane, h and out from y and prop (60 of its 118
+// MFMAs per tile and wave); f2_bwd_saved below reads h's hi plane and out from the forward instead.
 template <bool BWD>
-__global__ __launch_bounds__(512, 1) void final2_kernel(F2Params p) {
+__device__ __forceinline__ void f2_chain(const F2Params& p) {
   extern __shared__ __attribute__((aligned(16))) u16 lds[];
   u16* const CH = lds; u16* const CL = lds + F2_TILE; u16* const HH = lds + 2 * F2_TILE; u16* const HL = lds + 3 * F2_TILE;
   u16* const DHH = lds + 4 * F2_TILE;                            // (backward) dh, hi plane
@@ -589,6 +666,7 @@ __global__ __launch_bounds__(512, 1) void final2_kernel(F2Params p) {
   const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)p.y_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)p.prop, 0, (int)p.p_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc((void*)(BWD ? (void*)p.gout : (void*)p.out), 0, (int)p.o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc((void*)p.hsave, 0, (int)p.h_bytes, 0x00020000);   // (forward, optional)
   u16* const W1S = reinterpret_cast<u16*>(red + 16 * F2_C + 64 * 8);                  // (backward) the output layer's pack, [16][F2_W1RS]
   const F2W w0 = f2_load_w(p.wp0, 16 * wave + fr, q);
   // the output layer's one cout tile (rows >= outc are zero): registers in the forward; the backward, which has none to spare
@@ -645,6 +723,8 @@ __global__ __launch_bounds__(512, 1) void final2_kernel(F2Params p) {
       f2_gemm<3, 4>(acc, w0, CH, CL, 0, fr, q);
       f2_store_relu_split(acc, b0, HH, HL, wave, fr, q);
       __syncthreads();
+      // (forward, when a backward will follow) h's hi plane leaves for f2_bwd_saved: the stores fly under the output layer
+      if (!BWD && p.hsave) f2_save_h(HH, hr, m0, tid);
       // ---- out = relu(W1 h + b1): wave w < 4 multiplies pixel tile w; lanes q hold couts 4 q .. 4 q + 3 of pixel 16 w + fr
       float ov[4] = {0.f, 0.f, 0.f, 0.f};
       if (wave < 4) {
@@ -753,37 +833,160 @@ __global__ __launch_bounds__(512, 1) void final2_kernel(F2Params p) {
       }
     }
   }
-  if (!BWD) return;
-  // ---- per-workgroup partials: dW0 [128][128] | dW1 [16][128] | db0 [128] | db1 [16]
-  float* ws = p.ws + (int64_t)blockIdx.x * F2_WS_PER_BLOCK;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ws[(16 * wave + 4 * q + e) * F2_C + 16 * j + fr] = gw0[j][e];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ws[F2_C * F2_C + (4 * q + e) * F2_C + 16 * wave + fr] = gw1[e];
-  __syncthreads();
-  float* redb = red;                                             // [16 pixel columns][128 channels], then [64 threads][4]
-#pragma unroll
-  for (int e = 0; e < 4; ++e) redb[fr * F2_C + 16 * wave + 4 * q + e] = sb0[e];
-  if (wave < 4 && q < 2) {                                       // (lanes q = 1 hold zeros when os == 4)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) redb[16 * F2_C + (16 * wave + fr) * 8 + 4 * q + e] = sb1[e];
-  }
-  __syncthreads();
-  if (tid < F2_C) {
-    float sacc = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sacc += redb[r * F2_C + tid];
-    ws[F2_C * F2_C + 16 * F2_C + tid] = sacc;
-  } else if (tid < F2_C + 16) {
-    const int c = tid - F2_C;
-    float sacc = 0.f;
-    if (c < 8)
-      for (int r = 0; r < 64; ++r) sacc += redb[16 * F2_C + r * 8 + c];
-    ws[F2_C * F2_C + 16 * F2_C + F2_C + c] = sacc;
-  }
+  if (BWD) f2_bwd_partials(p.ws + (int64_t)blockIdx.x * F2_WS_PER_BLOCK, red, gw0, gw1, sb0, sb1, tid);
 }
+
+// ------------------------------------------------------------------ PathNet.final backward on the forward's saved tensors
+// What f2_chain<true> uses of the tensors it rebuilds: of out its sign, of h its hi plane (the ReLU gate and the one-term dW1), of
+// c its hi plane (the one-term dW0).  The forward has all three: out is its result, and h's hi plane can leave its LDS tile as
+// one bf16 plane (256 B per pixel: wcmc_final2_fwd_save).  This backward loads them instead of multiplying for them -- 58 MFMAs
+// per 64-pixel tile and wave instead of 118, no W0 fragments, no W1 pack, no lo plane, three barriers per sample instead of
+// five -- and runs every MFMA that remains on the same operands in the same order on the same grid, so the eight results are
+// BIT-IDENTICAL to f2_chain<true>'s.  (The forward's out = relu(..) is the value f2_chain<true> recomputes, same MFMA sequence, so
+// [stored out > 0] is its gate; the debug build's wave-private forward, whose out can differ in the last ulp, writes no plane.)
+__device__ __forceinline__ void f2_bwd_saved(const F2Params& p) {
+  extern __shared__ __attribute__((aligned(16))) u16 lds[];
+  u16* const CH = lds; u16* const HH = lds + F2_TILE;            // c and h, hi planes
+  u16* const DHH = lds + 2 * F2_TILE;                            // dh, hi plane
+  float* const stg = reinterpret_cast<float*>(lds + 3 * F2_TILE);      // d_y tile [64][68]
+  u16* const DOH = lds + 4 * F2_TILE;                            // gated d_out, hi plane, [64][F2_ORS]
+  float* const red = reinterpret_cast<float*>(lds + 4 * F2_TILE + E3_TP * F2_ORS);    // bias sums [16][128] + [64][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, q = lane >> 4;
+  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)p.y_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)p.prop, 0, (int)p.p_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc((void*)p.gout, 0, (int)p.o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)p.o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc((void*)p.hsave, 0, (int)p.h_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (int)p.dy_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dpr = __builtin_amdgcn_make_buffer_rsrc((void*)p.dprop, 0, (int)p.dp_bytes, 0x00020000);
+  const int oq = p.os >> 2;
+  const int64_t tpi = p.HW / E3_TP;
+  const int64_t nsuper = (int64_t)p.B * tpi;
+  // d_out and out of pixel 16 wave + fr, channels 4 q .. 4 q + 3: waves 0..3, lanes q < oq
+  const bool od = wave < 4 && q < oq;
+  const unsigned oo = (unsigned)((16 * wave + fr) * p.os * 4 + q * 16);
+
+  const F2W t0 = f2_load_w(p.wt0, 16 * wave + fr, q);            // W0^T rows of this wave's concat-channel tile
+  const u16* a1 = p.wt1 + (int64_t)((16 * wave + fr) * 2) * 32 + q * 8;
+  const bf16x8 t1h = *reinterpret_cast<const bf16x8*>(a1), t1l = *reinterpret_cast<const bf16x8*>(a1 + 32);      // W1^T rows, hidden-channel tile
+  f32x4 gw0[8], gw1 = f32x4{0.f, 0.f, 0.f, 0.f};                 // dW0[co tile = wave][8 ci tiles], dW1[16][ci tile = wave]
+#pragma unroll
+  for (int j = 0; j < 8; ++j) gw0[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float sb0[4] = {0.f, 0.f, 0.f, 0.f}, sb1[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < E3_TP * F2_ORS / 2; i += 512) reinterpret_cast<unsigned*>(DOH)[i] = 0u;       // channels >= os stay zero
+
+  for (int64_t st = blockIdx.x; st < nsuper; st += gridDim.x) {
+    const int64_t b = st / tpi, hw0 = (st - b * tpi) * E3_TP;
+    int64_t m0 = (b * p.S) * p.HW + hw0;
+    F2Pre pp = f2_load64(pr, b * p.HW + hw0, p.p_ps, tid);
+    // sample 0's tiles; inside the loop the next sample's fly under the GEMMs
+    F2Pre yp = f2_load64(yr, m0, p.y_ps, tid);
+    F2Pre hp = f2_load_h(hr, m0, tid);
+    u32x4 go = {0u, 0u, 0u, 0u}, so = {0u, 0u, 0u, 0u};
+    if (od) {
+      go = __builtin_amdgcn_raw_buffer_load_b128(gr, (unsigned)(m0 * p.os * 4) + oo, 0, 0);
+      so = __builtin_amdgcn_raw_buffer_load_b128(sr, (unsigned)(m0 * p.os * 4) + oo, 0, 0);
+    }
+    __syncthreads();                                             // (the tiles' last readers are done; before the first tile: DOH is zeroed)
+    f2_store64_hi(pp, CH, 64, tid);
+    f32x4 dpacc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dpacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.S; ++s, m0 += p.HW) {
+      f2_store64_hi(yp, CH, 0, tid);
+      f2_store_h(hp, HH, tid);
+      // ---- d_o = d_out . [out > 0] (hi plane into its tile; exact sums = the output layer's bias gradient): registers only
+      if (od) {
+        u16 hi[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = e3_u2f(so[e]) > 0.f ? e3_u2f(go[e]) : 0.f;
+          sb1[e] += d;
+          hi[e] = e3_bf(d);
+        }
+        *reinterpret_cast<u32x2*>(DOH + (16 * wave + fr) * F2_ORS + 4 * q) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+      }
+      if (s + 1 < p.S) {
+        const int64_t m1 = m0 + p.HW;
+        yp = f2_load64(yr, m1, p.y_ps, tid);
+        hp = f2_load_h(hr, m1, tid);
+        if (od) {
+          go = __builtin_amdgcn_raw_buffer_load_b128(gr, (unsigned)(m1 * p.os * 4) + oo, 0, 0);
+          so = __builtin_amdgcn_raw_buffer_load_b128(sr, (unsigned)(m1 * p.os * 4) + oo, 0, 0);
+        }
+      }
+      __syncthreads();
+      // ---- dh = (W1^T d_o) . [h > 0]: this wave's hidden-channel tile, k = the 32-wide step whose channels >= os are zero
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bf16x8 dof = *reinterpret_cast<const bf16x8*>(DOH + (16 * i + fr) * F2_ORS + q * 8);
+        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1l, dof, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1h, dof, a, 0, 0, 0);
+        const int o = (16 * i + fr) * F2_RS + 16 * wave + 4 * q;
+        const u32x2 hm = *reinterpret_cast<const u32x2*>(HH + o);
+        u16 hi[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const u16 hv = (u16)((e < 2 ? hm[0] : hm[1]) >> (16 * (e & 1)));
+          const float d = e3_f(hv) > 0.f ? a[e] : 0.f;
+          sb0[e] += d;
+          hi[e] = e3_bf(d);
+        }
+        *reinterpret_cast<u32x2*>(DHH + o) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+      }
+      __syncthreads();
+      // ---- dc = W0^T dh: waves 0..3 hold d_y (concat channels 0..63), waves 4..7 the d_prop contribution of this sample
+      f32x4 acc[4];
+      f2_gemm<2, 4>(acc, t0, DHH, nullptr, 0, fr, q);
+      if (wave < 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          *reinterpret_cast<float4*>(stg + (16 * i + fr) * 68 + 16 * wave + 4 * q) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dpacc[i] += acc[i];
+      }
+      // ---- weight gradients (hi x hi, pixels on k): dW0[co tile = wave][ci tile j] += dh^T c;  dW1[16][ci tile = wave] += d_o^T h
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 a0 = f2_tr(DHH, F2_RS, kk, wave, lane);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gw0[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, f2_tr(CH, F2_RS, kk, j, lane), gw0[j], 0, 0, 0);
+        gw1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2_tr(DOH, F2_ORS, kk, 0, lane), f2_tr(HH, F2_RS, kk, wave, lane), gw1, 0, 0, 0);
+      }
+      __syncthreads();
+      // d_y tile: whole 256-byte rows
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int v = tid + 512 * k, px = v >> 4, c4 = (v & 15) * 4;
+        const float4 o = *reinterpret_cast<const float4*>(stg + px * 68 + c4);
+        const u32x4 o4 = {__builtin_bit_cast(unsigned, o.x), __builtin_bit_cast(unsigned, o.y), __builtin_bit_cast(unsigned, o.z),
+                          __builtin_bit_cast(unsigned, o.w)};
+        __builtin_amdgcn_raw_buffer_store_b128(o4, dyr, (unsigned)(m0 * 256) + (unsigned)(px * 256 + c4 * 4), 0, 0);
+      }
+      // (no barrier here: the next sample's c, h and d_o go into tiles nobody reads any more -- their readers sit before the
+      // barrier above -- and two barriers stand between these reads of the staging tile and its next writes)
+    }
+    if (wave >= 4) {                                             // d_prop of the super-tile: the sum over its S samples
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const u32x4 o4 = {e3_f2u(dpacc[i][0]), e3_f2u(dpacc[i][1]), e3_f2u(dpacc[i][2]), e3_f2u(dpacc[i][3])};
+        __builtin_amdgcn_raw_buffer_store_b128(o4, dpr, (unsigned)((b * p.HW + hw0) * 256) + (unsigned)((16 * i + fr) * 256 + (16 * (wave - 4) + 4 * q) * 4), 0, 0);
+      }
+    }
+  }
+  f2_bwd_partials(p.ws + (int64_t)blockIdx.x * F2_WS_PER_BLOCK, red, gw0, gw1, sb0, sb1, tid);
+}
+
+// The kernels.  final2_kernel<false> / <true> are the names the default step launches (bench.py's classes final2_fwd / final2_bwd):
+// the forward, and the backward on the saved tensors; the recomputing backward of wcmc_final2_bwd has a name of its own.
+template <bool BWD>
+__global__ __launch_bounds__(512, 1) void final2_kernel(F2Params p) {
+  if (BWD) f2_bwd_saved(p);
+  else f2_chain<false>(p);
+}
+__global__ __launch_bounds__(512, 1) void final2_recompute_bwd_kernel(F2Params p) { f2_chain<true>(p); }
 
 __global__ __launch_bounds__(256) void final2_bwd_finish_kernel(const float* __restrict__ ws, int nblk, int outc, float* __restrict__ dw0,
                                                                 float* __restrict__ db0, float* __restrict__ dw1, float* __restrict__ db1) {
@@ -976,6 +1179,9 @@ static int f2_grid() { return 256; }
 constexpr size_t F2_LDS_FWD = (size_t)4 * F2_TILE * sizeof(u16);
 constexpr size_t F2_LDS_BWD = (size_t)5 * F2_TILE * sizeof(u16) + (size_t)E3_TP * F2_ORS * sizeof(u16) + (size_t)(16 * F2_C + 64 * 8) * sizeof(float) +
                               (size_t)16 * F2_W1RS * sizeof(u16);
+// (saved backward: c, h, dh hi planes + the d_y staging tile in a tile of its own + d_o + the bias sums)
+constexpr size_t F2_LDS_BWD_SAVED = (size_t)4 * F2_TILE * sizeof(u16) + (size_t)E3_TP * F2_ORS * sizeof(u16) + (size_t)(16 * F2_C + 64 * 8) * sizeof(float);
+static_assert((size_t)E3_TP * 68 * sizeof(float) <= (size_t)F2_TILE * sizeof(u16), "the d_y staging tile fits a tile plane");
 
 static int e3_grid_bwd() { return 256; }
 
@@ -1081,13 +1287,18 @@ static int f2_fill(F2Params& p, const float* y, int y_ps, const float* prop, int
   return 0;
 }
 
-extern "C" int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* stream) {
+// save: h's hi plane leaves with out (wcmc_final2_fwd_save); always final2_kernel<false> then -- the wave-private experiment writes no plane
+static int f2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW, const void* wp0,
+                  const float* b0, const void* wp1, const float* b1, int outc, float* out, bool save, void* h_hi, void* stream) {
   F2Params p = {};
   if (int rc = f2_fill(p, y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc)) return rc;
   WCMC_REQUIRE(out && aligned16(out), WCMC_ERR_BAD_ARG, "final2_fwd: bad output");
   p.out = out;
-  {
+  if (save) {
+    WCMC_REQUIRE(h_hi, WCMC_ERR_BAD_ARG, "final2_fwd_save: null h_hi");
+    WCMC_REQUIRE(aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_fwd_save: h_hi must be 16-byte aligned");
+    p.hsave = (u16*)h_hi; p.h_bytes = (unsigned)((int64_t)B * S * HW * 256);      // (< 2 GiB: f2_fill)
+  } else {
     const char* e = ab_env("WCMC_F2W");                     // (debug build) 0: the cout-tile-per-wave kernel of round 3; 2: 32 pixels per wave; 1: 16
     if (e && e[0] != '0') {
       const int ni = e[0] == '2' ? 2 : 1;
@@ -1108,25 +1319,62 @@ extern "C" int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* 
   return check_launch("final2_fwd");
 }
 
-extern "C" int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                               const void* wt1, const float* gout, float* dy, float* dprop, float* dw0, float* db0, float* dw1,
-                               float* db1, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* stream) {
+  return f2_fwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, out, false, nullptr, stream);
+}
+extern "C" int wcmc_final2_fwd_save(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                                    const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
+                                    void* stream) {
+  return f2_fwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, out, true, h_hi, stream);
+}
+
+// saved: the backward on the forward's out and h_hi (wcmc_final2_bwd_saved); else the recomputing one
+static int f2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                  const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
+                  const void* wt1, const float* gout, bool saved, const float* out, const void* h_hi, float* dy, float* dprop, float* dw0,
+                  float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream) {
   F2Params p = {};
   if (int rc = f2_fill(p, y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc)) return rc;
   WCMC_REQUIRE(wt0 && wt1 && gout && dy && dprop && dw0 && db0 && dw1 && db1 && workspace && aligned16(wt0) && aligned16(wt1) &&
                    aligned16(gout) && aligned16(dy) && aligned16(dprop) && aligned16(workspace),
                WCMC_ERR_BAD_ARG, "final2_bwd: bad argument");
+  if (saved) {
+    WCMC_REQUIRE(out && h_hi, WCMC_ERR_BAD_ARG, "final2_bwd_saved: null out or h_hi");
+    WCMC_REQUIRE(aligned16(out) && aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_bwd_saved: out and h_hi must be 16-byte aligned");
+  }
   WCMC_REQUIRE(workspace_bytes >= wcmc_final2_bwd_workspace_bytes(), WCMC_ERR_WORKSPACE, "final2_bwd: workspace too small");
   p.wt0 = (const u16*)wt0; p.wt1 = (const u16*)wt1; p.gout = gout; p.dy = dy; p.dprop = dprop; p.ws = (float*)workspace;
   const int64_t M = (int64_t)B * S * HW;
   p.dy_bytes = (unsigned)(M * 256); p.dp_bytes = (unsigned)((int64_t)B * HW * 256);
-  static LdsAttr attr;
-  if (set_max_lds(reinterpret_cast<const void*>(&final2_kernel<true>), (size_t)F2_LDS_BWD, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
   const int nblk = f2_grid();
-  hipLaunchKernelGGL(final2_kernel<true>, dim3((unsigned)nblk), dim3(512), F2_LDS_BWD, (hipStream_t)stream, p);
+  if (saved) {
+    p.out = const_cast<float*>(out); p.hsave = (u16*)const_cast<void*>(h_hi); p.h_bytes = (unsigned)(M * 256);      // (read only; < 2 GiB: f2_fill)
+    static LdsAttr attrs;
+    if (set_max_lds(reinterpret_cast<const void*>(&final2_kernel<true>), (size_t)F2_LDS_BWD_SAVED, attrs) != hipSuccess) return WCMC_ERR_LAUNCH;
+    hipLaunchKernelGGL(final2_kernel<true>, dim3((unsigned)nblk), dim3(512), F2_LDS_BWD_SAVED, (hipStream_t)stream, p);
+  } else {
+    static LdsAttr attr;
+    if (set_max_lds(reinterpret_cast<const void*>(&final2_recompute_bwd_kernel), (size_t)F2_LDS_BWD, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
+    hipLaunchKernelGGL(final2_recompute_bwd_kernel, dim3((unsigned)nblk), dim3(512), F2_LDS_BWD, (hipStream_t)stream, p);
+  }
   if (int rc = check_launch("final2_bwd")) return rc;
   hipLaunchKernelGGL(final2_bwd_finish_kernel, dim3((unsigned)((F2_WS_PER_BLOCK + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float*)workspace, nblk, outc, dw0, db0, dw1, db1);
   return check_launch("final2_bwd_finish");
+}
+
+extern "C" int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
+                               const void* wt1, const float* gout, float* dy, float* dprop, float* dw0, float* db0, float* dw1,
+                               float* db1, void* workspace, size_t workspace_bytes, void* stream) {
+  return f2_bwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, wt0, wt1, gout, false, nullptr, nullptr, dy, dprop,
+                dw0, db0, dw1, db1, workspace, workspace_bytes, stream);
+}
+extern "C" int wcmc_final2_bwd_saved(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                                     const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
+                                     const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
+                                     float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream) {
+  return f2_bwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, wt0, wt1, gout, true, out, h_hi, dy, dprop,
+                dw0, db0, dw1, db1, workspace, workspace_bytes, stream);
 }

@@ -77,6 +77,11 @@ FUSE_EMBED = os.environ.get("WCMC_FUSE_EMBED", "1") != "0"
 # WCMC_FUSE_FINAL=0: A/B switch back to concatenation + fused layer pair (csrc/pathnet_fused.hip; default mode only)
 FUSE_FINAL = os.environ.get("WCMC_FUSE_FINAL", "1") != "0"
 
+# The fused final chain's forward hands the hi plane of its hidden activation (bf16, 256 B per pixel) and its output to the backward
+# (wcmc_final2_fwd_save / _bwd_saved) instead of the backward recomputing both (wcmc_final2_bwd): same results bit for bit, 60 of
+# 118 MFMAs per tile and wave fewer, +268 MB live per PathNet between forward and backward at the benchmark shape.  False: recompute.
+SAVE_FINAL_HIDDEN = True
+
 # (weight-gradient, data-gradient) MFMAs per product of the chains with a given filter size, where they differ from the mode's:
 # the rung table of the backward GEMMs (profiles/r06_grad_rungs.txt; empty = the mode's rungs everywhere)
 TERMS_BY_KS = {}

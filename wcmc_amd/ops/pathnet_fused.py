@@ -77,8 +77,11 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
 
 
 class _FinalFusedX(torch.autograd.Function):
-    """``chain2(cat([flat, repeat_S(prop)], 1))`` (networks.py:39-42) as one launch per direction (``wcmc_final2_*``): neither
-    the 128-channel concatenation nor the hidden activation is written; the backward recomputes them."""
+    """``chain2(cat([flat, repeat_S(prop)], 1))`` (networks.py:39-42) as one launch per direction (``wcmc_final2_*``): the
+    128-channel concatenation is never written.  Of the hidden activation the backward needs the bf16 hi plane only and of the
+    output its sign: with ``ops.SAVE_FINAL_HIDDEN`` a forward that a backward will follow writes that plane ([M][128] bf16)
+    beside the output and the backward reads both (``wcmc_final2_fwd_save`` / ``_bwd_saved``); otherwise nothing is kept and the
+    backward recomputes the chain (``wcmc_final2_bwd``).  Same results bit for bit."""
 
     @staticmethod
     def forward(ctx, flat, prop, s, *params):
@@ -89,18 +92,26 @@ class _FinalFusedX(torch.autograd.Function):
         packs = _pack_chain_x([params[0], params[2]], 1)
         osz = 4 if outc <= 4 else 8                           # pixel stride of the output: round_up(outc, 4)
         buf = torch.empty((bs, h, w, osz), device=flat.device, dtype=torch.float32)
-        with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz), "byte"):
-            check(lib().wcmc_final2_fwd(_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
-                                        _ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), outc,
-                                        _ptr(buf), _stream()), "final2_fwd")
+        args = (_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
+                _ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), outc, _ptr(buf))
+        saved = ()
+        if _sw.SAVE_FINAL_HIDDEN and any(ctx.needs_input_grad):
+            # h's hi plane: 128 bf16 = 64 floats' worth of bytes per pixel, written here and read once by the backward
+            hhi = torch.empty((bs * h * w, 128), device=flat.device, dtype=torch.bfloat16)
+            with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz + 64), "byte"):
+                check(lib().wcmc_final2_fwd_save(*args, _ptr(hhi), _stream()), "final2_fwd_save")
+            saved = (hhi, buf)       # (buf through save_for_backward: its version counter guards the output the caller holds)
+        else:
+            with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz), "byte"):
+                check(lib().wcmc_final2_fwd(*args, _stream()), "final2_fwd")
         ctx.geom, ctx.packs = (b, s, h, w, outc), packs
-        ctx.save_for_backward(flat, prop, *params)
+        ctx.save_for_backward(flat, prop, *params, *saved)
         return buf.permute(0, 3, 1, 2)[:, :outc]
 
     @staticmethod
     def backward(ctx, g):
         b, s, h, w, outc = ctx.geom
-        flat, prop, w0, b0, w1, b1 = ctx.saved_tensors
+        flat, prop, w0, b0, w1, b1, *saved = ctx.saved_tensors
         g = _as_nhwc_nograd(g)
         osz = 4 if outc <= 4 else 8
         if not (_dense_pixel_stride(g) == osz):
@@ -113,11 +124,16 @@ class _FinalFusedX(torch.autograd.Function):
         nb = lib().wcmc_final2_bwd_workspace_bytes()
         ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         packs = ctx.packs
-        with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s), "byte"):
-            check(lib().wcmc_final2_bwd(_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
-                                        _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), outc, _ptr(packs[0][1]), _ptr(packs[1][1]),
-                                        _ptr(g), _ptr(dy), _ptr(dprop), _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(ws), nb,
-                                        _stream()), "final2_bwd")
+        ins = (_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
+               _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), outc, _ptr(packs[0][1]), _ptr(packs[1][1]), _ptr(g))
+        outs = (_ptr(dy), _ptr(dprop), _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(ws), nb, _stream())
+        if saved:
+            hhi, buf = saved
+            with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s + 64 + osz), "byte"):
+                check(lib().wcmc_final2_bwd_saved(*ins, _ptr(buf), _ptr(hhi), *outs), "final2_bwd_saved")
+        else:
+            with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s), "byte"):
+                check(lib().wcmc_final2_bwd(*ins, *outs), "final2_bwd")
         return (dy if ctx.needs_input_grad[0] else None, dprop if ctx.needs_input_grad[1] else None, None, dw0, db0, dw1, db1)
 
 
