@@ -241,6 +241,23 @@ int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const void* wp0, co
                     const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride,
                     const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0,
                     float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two launches reading x WHERE IT LIES: fp32, channel-first -- N = M / HW samples of Cin channel planes of HW floats,
+ * sample / channel stride x_sample_stride / x_channel_stride floats (a slice of a larger buffer in N and C is fine), each H x W
+ * plane contiguous -- instead of its split copy (`paths` arrives channel-first, support/networks.py:31-33, and this chain is its
+ * only reader: the split copy was a pass over memory of its own).  The kernels load a tile's Cin rows of 64 pixels and split them
+ * with wcmc_split_from_nchw's arithmetic on the way into the LDS tile, so y, y_mean and the six gradients equal those of the
+ * x_split entries BIT FOR BIT.  wcmc_embed3_nchw_supported (host only, no device needed): Cin <= 64, H * W % 64 == 0 (a 64-pixel
+ * tile lies in one sample), sw == 1 and sh == W (a contiguous plane), sc >= H * W; anything else takes the split copy.  x needs
+ * 4-byte alignment only. */
+int wcmc_embed3_nchw_supported(int Cin, int64_t N, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw);
+int wcmc_embed3_mean_fwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin,
+                              const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
+                              const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream);
+int wcmc_embed3_bwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin, const void* wp0,
+                         const float* b0, const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy,
+                         int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0,
+                         float* db0, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
+                         void* stream);
 /* ---------------------------------------------------------------- PathNet.final, fused (support/networks.py:39-42)
  * out = ConvChain(128 -> 128 -> outc <= 8, ksize 1, ReLU, ReLU)(cat([y, repeat_S(prop)], 1)): y fp32 over M = B*S*HW pixels
  * (64 channels, pixel stride y_pixel_stride floats), prop fp32 over B*HW pixels (64 channels), out / gout fp32 [M][os] with

@@ -11,8 +11,12 @@ with open(f, newline="") as fh:
     for r in csv.DictReader(fh):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", ""), r.get("Stream_Id", "")))
 rows.sort()
-# steps: the captured step begins with the one nchw_split launch (the shared `paths` conversion)
+# steps: the captured step begins with the one nchw_split launch (the shared `paths` conversion).  Since the embeddings read `paths`
+# in place that launch is gone: a step (eager or replayed) is then cut at the first of its two embed3_fwd launches -- the window
+# starts a few kernels into the step (behind the head and the diffuse half's weight-norm launch) and ends as far into the next
 steps = [i for i, r in enumerate(rows) if "nchw_split_kernel" in r[2]]
+if not steps:
+    steps = [i for i, r in enumerate(rows) if "embed3_fwd_kernel" in r[2]][::2]
 print("kernels %d, steps found %d" % (len(rows), len(steps)))
 for a, b in list(zip(steps[:-1], steps[1:]))[8:14]:
     seg = rows[a:b]

@@ -45,6 +45,8 @@ __device__ __forceinline__ unsigned e3_f2u(float v) { return __builtin_bit_cast(
 
 struct E3Params {
   const u16* x; int64_t M; int Cp0, Kt0;              // split input [M][2][Cp0]; k extent of layer 0's pack (32 or 64)
+  const float* xf; int64_t xsn, xsc;                  // NCHW kernels: the fp32 channel-first source instead (sample / channel stride in floats;
+                                                      // the H x W plane contiguous, HW % 64 == 0); x_bytes = one sample's extent from a tile's first pixel
   const u16* wp0; const u16* wp1; const u16* wp2;     // forward packs [64][2][64]
   const float* b0; const float* b1; const float* b2;
   float* y;                                           // forward: fp32 [M][64]
@@ -142,12 +144,58 @@ __device__ __forceinline__ void e3_store_x(const E3XPre<NT>& r, u16* xh, u16* xl
   }
 }
 
+// The x tile read where it lies (NCHW): fp32, channel-first, the tile's 64 pixels one 256-byte run in each of the Cin channel rows
+// of ONE sample (HW % 64 == 0).  The same 1024 units of four dwords, a unit now being (pixel, channel quad): four dword loads, one per
+// channel row -- a wave's load instruction covers 64-byte runs of four rows -- split with split1's arithmetic (conv_bf16x3.hip:
+// nchw_split_kernel) on the way into LDS, so the tile holds what the split copy held bit for bit (channels >= Cin: zeros, from
+// loads behind the sample's extent).  Unit v = tid + NT k: bits [1:0] [5:4] [9:8] of v are the pixel, [3:2] [7:6] the channel quad --
+// the 16 lanes that one pass of an 8-byte LDS store serves hold 4 pixels x 4 quads, i.e. 32 different banks at E3_RS = 80.
+__device__ __forceinline__ void e3_unit_nchw(int v, int& px, int& cq) {
+  px = (v & 3) | ((v >> 2) & 12) | ((v >> 4) & 48);
+  cq = ((v >> 2) & 3) | ((v >> 4) & 12);
+}
+// (m0 is wave-uniform and < 2^23, checked by the host: sample and plane offset in scalar 32-bit arithmetic)
+template <int NT>
+__device__ __forceinline__ E3XPre<NT> e3_load_x_nchw(const E3Params& p, int64_t m0, int tid) {
+  E3XPre<NT> r;
+  const unsigned n = (unsigned)m0 / (unsigned)p.HW, hw0 = (unsigned)m0 - n * (unsigned)p.HW;
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.xf + (int64_t)n * p.xsn + hw0), 0, (int)p.x_bytes, 0x00020000);
+  const unsigned sc4 = (unsigned)p.xsc * 4u;                  // (64 * xsc * 4 < 2 GiB: checked by the host)
+#pragma unroll
+  for (int k = 0; k < 1024 / NT; ++k) {
+    int px, cq;
+    e3_unit_nchw(tid + NT * k, px, cq);
+    const unsigned off = (unsigned)(4 * cq) * sc4 + (unsigned)(px * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r.v[k][e] = __builtin_amdgcn_raw_buffer_load_b32(xr, off + (unsigned)e * sc4, 0, 0);
+  }
+  return r;
+}
+template <int NT>
+__device__ __forceinline__ void e3_store_x_nchw(const E3XPre<NT>& r, u16* xh, u16* xl, int tid) {
+#pragma unroll
+  for (int k = 0; k < 1024 / NT; ++k) {
+    int px, cq;
+    e3_unit_nchw(tid + NT * k, px, cq);
+    u16 hi[4], lo[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float f = e3_u2f(r.v[k][e]);
+      hi[e] = e3_bf(f);
+      lo[e] = e3_bf(f - e3_f(hi[e]));
+    }
+    const int o = px * E3_RS + 4 * cq;
+    *reinterpret_cast<u32x2*>(xh + o) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+    *reinterpret_cast<u32x2*>(xl + o) = u32x2{(unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16)};
+  }
+}
+
 // ------------------------------------------------------------------ forward
 // MEAN: the spp mean of y (support/networks.py:35-36) leaves with it.  A workgroup then walks SUPER-tiles -- the same 64 pixels
 // of an image's S samples, one after the other -- and keeps the running sum of its y fragments in registers: s ascending, fp32
 // adds, one multiply by 1 / S at the end, i.e. the sums wcmc_spp_reduce forms from the stored y (bit-identical), without
 // reading y (268 MB at the benchmark shape) again.  Needs HW % 64 == 0.
-template <bool MEAN>
+template <bool MEAN, bool NCHW>
 __global__ __launch_bounds__(256, 3) void embed3_fwd_kernel(E3Params p) {
   __shared__ __attribute__((aligned(16))) u16 lds[4 * E3_TILE];
   u16* const XH = lds; u16* const XL = lds + E3_TILE; u16* const AH = lds + 2 * E3_TILE; u16* const AL = lds + 3 * E3_TILE;
@@ -168,19 +216,24 @@ __global__ __launch_bounds__(256, 3) void embed3_fwd_kernel(E3Params p) {
     const int64_t b = u / tpi;
     return (b * p.S + sidx) * p.HW + (u - b * tpi) * E3_TP;
   };
+  auto load_x = [&](int64_t m0) {
+    if constexpr (NCHW) return e3_load_x_nchw<256>(p, m0, tid);
+    else return e3_load_x<256>(xr, m0, p.M, p.Cp0, tid);
+  };
   int64_t u = blockIdx.x;
   E3XPre<256> pre;
-  if (u < nunits) pre = e3_load_x<256>(xr, first_pixel(u, 0), p.M, p.Cp0, tid);
+  if (u < nunits) pre = load_x(first_pixel(u, 0));
   for (; u < nunits; u += gridDim.x) {
     f32x4 msum[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) msum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int sidx = 0; sidx < per; ++sidx) {
-      e3_store_x<256>(pre, XH, XL, tid);
+      if constexpr (NCHW) e3_store_x_nchw<256>(pre, XH, XL, tid);
+      else e3_store_x<256>(pre, XH, XL, tid);
       {                                                                          // next tile's loads fly under this tile's GEMMs
         const bool more = sidx + 1 < per;
         const int64_t un = more ? u : u + gridDim.x;
-        if (un < nunits) pre = e3_load_x<256>(xr, first_pixel(un, more ? sidx + 1 : 0), p.M, p.Cp0, tid);
+        if (un < nunits) pre = load_x(first_pixel(un, more ? sidx + 1 : 0));
       }
       __syncthreads();
       f32x4 acc[4];
@@ -254,6 +307,7 @@ __device__ __forceinline__ bf16x8 e3_tr(const u16* tile, int kk, int ct, int lan
 // 2 ph, 2 ph + 1, and the weight-gradient tiles (cout tile ct) x (cin tiles 2 ph, 2 ph + 1) of the three layers -- half the
 // accumulators and half the prefetch registers of a four-wave layout, which spilled (40 VGPRs to scratch inside the loop: the
 // kernel ran at 1.2 TB/s).
+template <bool NCHW>
 __global__ __launch_bounds__(512, 1) void embed3_bwd_kernel(E3Params p) {
   __shared__ __attribute__((aligned(16))) u16 lds[7 * E3_TILE];
   __shared__ float red[3][32][64];
@@ -308,12 +362,17 @@ __global__ __launch_bounds__(512, 1) void embed3_bwd_kernel(E3Params p) {
     }
     return r;
   };
+  auto load_x = [&](int64_t m0) {
+    if constexpr (NCHW) return e3_load_x_nchw<512>(p, m0, tid);
+    else return e3_load_x<512>(xr, m0, p.M, p.Cp0, tid);
+  };
   int64_t t = blockIdx.x;
   E3XPre<512> pre;
   DyPre dpre;
-  if (t < ntiles) { pre = e3_load_x<512>(xr, t * E3_TP, p.M, p.Cp0, tid); dpre = load_dy(t * E3_TP); }
+  if (t < ntiles) { pre = load_x(t * E3_TP); dpre = load_dy(t * E3_TP); }
   for (; t < ntiles; t += gridDim.x) {
-    e3_store_x<512>(pre, XH, XL, tid);
+    if constexpr (NCHW) e3_store_x_nchw<512>(pre, XH, XL, tid);
+    else e3_store_x<512>(pre, XH, XL, tid);
     // dy = g_y + g_mean / S: hi plane into its tile, exact column sums (the last layer's bias gradient) on the side
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -328,7 +387,7 @@ __global__ __launch_bounds__(512, 1) void embed3_bwd_kernel(E3Params p) {
       *reinterpret_cast<u32x2*>(DYH + px * E3_RS + c4) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
     }
     const int64_t tn = t + gridDim.x;
-    if (tn < ntiles) { pre = e3_load_x<512>(xr, tn * E3_TP, p.M, p.Cp0, tid); dpre = load_dy(tn * E3_TP); }
+    if (tn < ntiles) { pre = load_x(tn * E3_TP); dpre = load_dy(tn * E3_TP); }
     __syncthreads();
     // Five barriers per tile: the two GEMMs that depend on nothing but the staged tile run in ONE interval (h0 = W0 x and
     // a = W2^T dy), and the ReLU gates are applied from registers -- the wave that multiplies cout tile ct of a layer for its
@@ -1195,13 +1254,34 @@ extern "C" int wcmc_embed3_supported(int Cin, int C1, int C2, int C3) {
 
 extern "C" size_t wcmc_embed3_bwd_workspace_bytes(void) { return (size_t)e3_grid_bwd() * E3_WS_PER_BLOCK * sizeof(float); }
 
+// The channel-first fp32 source the *_nchw entries read in place: N samples of Cin channel planes of H x W floats.
+extern "C" int wcmc_embed3_nchw_supported(int Cin, int64_t N, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
+  if (!(Cin >= 1 && Cin <= 64 && N > 0 && H > 0 && W > 0 && H <= 0x7fffffff / W)) return 0;
+  const int64_t HW = H * W;
+  return HW % E3_TP == 0 &&                                 // a 64-pixel tile lies in one sample
+         sw == 1 && (H == 1 || sh == W) &&                  // ... and is one 256-byte run of every channel row
+         sc >= HW && sc < (0x7ff00000ll >> 8) &&            // channel rows apart (rows behind Cin are then behind a sample's extent); 64 rows in 31 bits
+         (N == 1 || sn >= 0) && N <= (0x7ff00000ll >> 8) / HW;
+}
+
+// (x_nchw != null: the source of the *_nchw entries -- sample / channel stride sn / sc in floats, HW pixels per plane -- else x_split)
 static int e3_fill(E3Params& p, const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                   const float* b1) {
-  WCMC_REQUIRE(x_split && wp0 && wp1 && b0 && b1 && M > 0 && Cin >= 1 && Cin <= 64, WCMC_ERR_BAD_ARG, "embed3: bad argument");
-  WCMC_REQUIRE(aligned16(x_split) && aligned16(wp0) && aligned16(wp1), WCMC_ERR_ALIGNMENT, "embed3: buffers must be 16-byte aligned");
-  p.x = (const u16*)x_split; p.M = M; p.Cp0 = round_up(Cin, 8); p.Kt0 = round_up(p.Cp0, 32);
+                   const float* b1, const float* x_nchw = nullptr, int64_t sn = 0, int64_t sc = 0, int64_t HW = 0) {
+  WCMC_REQUIRE((x_split || x_nchw) && wp0 && wp1 && b0 && b1 && M > 0 && Cin >= 1 && Cin <= 64, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  WCMC_REQUIRE((x_nchw || aligned16(x_split)) && aligned16(wp0) && aligned16(wp1), WCMC_ERR_ALIGNMENT, "embed3: buffers must be 16-byte aligned");
+  p.M = M; p.Cp0 = round_up(Cin, 8); p.Kt0 = round_up(p.Cp0, 32);
   p.wp0 = (const u16*)wp0; p.wp1 = (const u16*)wp1; p.b0 = b0; p.b1 = b1;
-  const int64_t xb = M * 4 * p.Cp0, yb = M * 256;
+  int64_t xb = M * 4 * p.Cp0;
+  const int64_t yb = M * 256;
+  if (x_nchw) {
+    WCMC_REQUIRE(((uintptr_t)x_nchw & 3) == 0, WCMC_ERR_ALIGNMENT, "embed3: the channel-first source must be 4-byte aligned");
+    WCMC_REQUIRE(HW > 0 && M % HW == 0 && wcmc_embed3_nchw_supported(Cin, M / HW, 1, HW, sn, sc, HW, 1), WCMC_ERR_BAD_ARG,
+                 "embed3: channel-first source not readable in place (ask wcmc_embed3_nchw_supported)");
+    p.xf = x_nchw; p.xsn = sn; p.xsc = sc; p.HW = HW;
+    xb = ((int64_t)(Cin - 1) * sc + E3_TP) * 4;             // what a tile may read, from its first pixel in channel 0
+  } else {
+    p.x = (const u16*)x_split;
+  }
   WCMC_REQUIRE(xb < 0x7ff00000ll && yb < 0x7ff00000ll, WCMC_ERR_BAD_ARG, "embed3: more than 2 GiB per tensor (split the batch)");
   p.x_bytes = (unsigned)xb; p.y_bytes = (unsigned)yb;
   return 0;
@@ -1215,17 +1295,17 @@ extern "C" int wcmc_embed3_fwd(const void* x_split, int64_t M, int Cin, const vo
   p.wp2 = (const u16*)wp2; p.b2 = b2; p.y = y;
   const int64_t ntiles = (M + E3_TP - 1) / E3_TP;
   const unsigned grid = (unsigned)(ntiles < 768 ? ntiles : 768);
-  hipLaunchKernelGGL(embed3_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(embed3_fwd_kernel<false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("embed3_fwd");
 }
 
 extern "C" int wcmc_embed3_mean_supported(int S, int64_t HW) { return S >= 1 && HW > 0 && HW % E3_TP == 0; }
 
-extern "C" int wcmc_embed3_mean_fwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                                    const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
-                                    void* stream) {
+static int e3_mean_fwd(const void* x_split, const float* x_nchw, int64_t sn, int64_t sc, int64_t M, int Cin, const void* wp0, const float* b0,
+                       const void* wp1, const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
+                       void* stream) {
   E3Params p = {};
-  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1)) return rc;
+  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, sn, sc, HW)) return rc;
   WCMC_REQUIRE(wp2 && b2 && y && y_mean && aligned16(wp2) && aligned16(y) && aligned16(y_mean), WCMC_ERR_BAD_ARG, "embed3_mean_fwd: bad argument");
   WCMC_REQUIRE(wcmc_embed3_mean_supported(S, HW) && M % ((int64_t)S * HW) == 0, WCMC_ERR_BAD_ARG,
                "embed3_mean_fwd: M must be B * S * HW with HW a multiple of 64 (ask wcmc_embed3_mean_supported)");
@@ -1233,16 +1313,31 @@ extern "C" int wcmc_embed3_mean_fwd(const void* x_split, int64_t M, int Cin, con
   p.S = S; p.HW = HW; p.gm_scale = 1.0f / (float)S;
   const int64_t nsuper = M / ((int64_t)S * E3_TP);
   const unsigned grid = (unsigned)(nsuper < 768 ? nsuper : 768);
-  hipLaunchKernelGGL(embed3_fwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  if (x_nchw) hipLaunchKernelGGL(HIP_KERNEL_NAME(embed3_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(embed3_fwd_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("embed3_mean_fwd");
 }
 
-extern "C" int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                               const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride,
-                               const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
-                               void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int wcmc_embed3_mean_fwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
+                                    const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
+                                    void* stream) {
+  WCMC_REQUIRE(x_split, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  return e3_mean_fwd(x_split, nullptr, 0, 0, M, Cin, wp0, b0, wp1, b1, wp2, b2, y, y_mean, S, HW, stream);
+}
+
+extern "C" int wcmc_embed3_mean_fwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin,
+                                         const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
+                                         const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream) {
+  WCMC_REQUIRE(x, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  return e3_mean_fwd(nullptr, x, x_sample_stride, x_channel_stride, M, Cin, wp0, b0, wp1, b1, wp2, b2, y, y_mean, S, HW, stream);
+}
+
+static int e3_bwd(const void* x_split, const float* x_nchw, int64_t sn, int64_t sc, int64_t M, int Cin, const void* wp0, const float* b0,
+                  const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride, const float* gm,
+                  int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
+                  void* workspace, size_t workspace_bytes, void* stream) {
   E3Params p = {};
-  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1)) return rc;
+  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, sn, sc, HW)) return rc;
   WCMC_REQUIRE(wt1 && wt2 && (gy || gm) && dw0 && db0 && dw1 && db1 && dw2 && db2 && workspace && aligned16(wt1) && aligned16(wt2) &&
                    (!gy || aligned16(gy)) && (!gm || aligned16(gm)) && aligned16(workspace),
                WCMC_ERR_BAD_ARG, "embed3_bwd: bad argument");
@@ -1258,11 +1353,31 @@ extern "C" int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const vo
   WCMC_REQUIRE(gyb < 0x7ff00000ll && gmb < 0x7ff00000ll, WCMC_ERR_BAD_ARG, "embed3_bwd: gradient view spans more than 2 GiB");
   p.gy_bytes = (unsigned)gyb; p.gm_bytes = (unsigned)gmb;
   const int nblk = e3_grid_bwd();
-  hipLaunchKernelGGL(embed3_bwd_kernel, dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream, p);
+  if (x_nchw) hipLaunchKernelGGL(embed3_bwd_kernel<true>, dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(embed3_bwd_kernel<false>, dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream, p);
   if (int rc = check_launch("embed3_bwd")) return rc;
   hipLaunchKernelGGL(embed3_bwd_finish_kernel, dim3((unsigned)((E3_WS_PER_BLOCK + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float*)workspace, nblk, Cin, dw0, db0, dw1, db1, dw2, db2);
   return check_launch("embed3_bwd_finish");
+}
+
+extern "C" int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
+                               const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride,
+                               const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  WCMC_REQUIRE(x_split, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  return e3_bwd(x_split, nullptr, 0, 0, M, Cin, wp0, b0, wp1, b1, wt1, wt2, gy, gy_pixel_stride, gm, gm_pixel_stride, S, HW, gm_scale, dw0, db0,
+                dw1, db1, dw2, db2, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wcmc_embed3_bwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin, const void* wp0,
+                                    const float* b0, const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy,
+                                    int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0,
+                                    float* db0, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  WCMC_REQUIRE(x, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  return e3_bwd(nullptr, x, x_sample_stride, x_channel_stride, M, Cin, wp0, b0, wp1, b1, wt1, wt2, gy, gy_pixel_stride, gm, gm_pixel_stride, S, HW,
+                gm_scale, dw0, db0, dw1, db1, dw2, db2, workspace, workspace_bytes, stream);
 }
 
 

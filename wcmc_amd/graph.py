@@ -8,8 +8,8 @@ Python -- four times as long as the MI355X needs to run them -- so the step is c
 
 * ``two_stream=True`` (what ``capture_validated`` builds for the launcher and the benchmark): the diffuse and the specular
   half of the step as two linear graphs replayed on two streams that ``ops.concurrent_stream_pair`` has shown to sit on
-  different hardware queues, between a head graph (step counter, the shared split of ``paths``) and a tail graph (radiance
-  metrics, guard, clip + Adam).  The pairings of ``FeatureMSE(rng='device')`` are drawn inside the graphs.
+  different hardware queues, between a head graph (step counter; the shared split of ``paths`` where the embeddings do not
+  read ``paths`` in place) and a tail graph (radiance metrics, guard, clip + Adam).  The pairings of ``FeatureMSE(rng='device')`` are drawn inside the graphs.
 * ``two_stream=False``: one forked graph (rounds 2-4); the overlap of its halves is up to hipGraphInstantiate.
 
 What stays eager is what talks to the host or other ranks: reading the non-finite-loss flags (``interfaces.py:254-257``; one
@@ -190,7 +190,8 @@ class GraphedTrainStep:
             fo.leave_grads = False                        # .grad must keep pointing at the captured buffers
 
     def _capture_halves(self, dev):
-        """Graphs of the two-stream step: ``graph_h`` (the shared split of ``paths``, on the launch stream), ``graph_d`` /
+        """Graphs of the two-stream step: ``graph_h`` (the step counter and, unless the embeddings read ``paths`` in place, its
+        shared split, on the launch stream; None when it would hold no launch), ``graph_d`` /
         ``graph_s`` (the halves, each on a stream and in a memory pool of its own: they run concurrently).  Returns the pool the
         tail graph shares (it runs after both halves, on the launch stream)."""
         itf = self.itf
@@ -200,7 +201,10 @@ class GraphedTrainStep:
         try:
             self.graph_h = None
             pre = getattr(itf.models.get('backbone_diffuse'), '_paths_nhwc', None) if itf.use_llpm_buf else None
-            keys = self.fm is not None and self.dev_keys
+            in_place = getattr(itf.models.get('backbone_diffuse'), '_paths_in_place', None) if pre is not None else None
+            if in_place is not None and in_place(self.static['paths']) is not None:
+                pre = None                                 # the embeddings read `paths` where it lies: no copy to make, and a head
+            keys = self.fm is not None and self.dev_keys   # with nothing to launch is not captured (an empty graph) at all
             if pre is not None or keys:
                 self.graph_h = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_h, capture_error_mode="thread_local"):

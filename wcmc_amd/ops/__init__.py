@@ -74,6 +74,10 @@ USE_BRANCH_STREAM = os.environ.get("WCMC_BRANCH_STREAM", "1") != "0"   # +1.8 % 
 # are recomputed in the backward.  Default mode only (its backward arithmetic is built in); WCMC_FUSE_EMBED=0: A/B switch.
 FUSE_EMBED = os.environ.get("WCMC_FUSE_EMBED", "1") != "0"
 
+# The fused embedding reads the channel-first `paths` where it lies (wcmc_embed3_*_nchw) instead of a split copy made by a pass of
+# its own in front of the step (pathnet_fused.py: embed_in_place); same results bit for bit.  WCMC_EMBED_IN_PLACE=0: A/B switch.
+EMBED_IN_PLACE = os.environ.get("WCMC_EMBED_IN_PLACE", "1") != "0"
+
 # WCMC_FUSE_FINAL=0: A/B switch back to concatenation + fused layer pair (csrc/pathnet_fused.hip; default mode only)
 FUSE_FINAL = os.environ.get("WCMC_FUSE_FINAL", "1") != "0"
 
@@ -163,7 +167,8 @@ from .conv_split import (_split_empty, split_raw, split_from_nchw_raw, presplit_
                          conv2d_wgrad_x_raw, _chainx_forward, _chainx_backward, _ConvChainX, _split_shared, _ChainSppMeanX,
                          _CatBroadcastChainX, _CatUpsampleChainX, conv_chain)
 from .pathnet_fused import (_dense_pixel_stride, _EmbedSppMeanFusedX, _FinalFusedX, cat_upsample_chain, _UNFUSED_NOTED,  # noqa: E402,F401
-                            _note_unfused, conv_chain_spp_mean, cat_broadcast_chain)
+                            _note_unfused, conv_chain_spp_mean, cat_broadcast_chain, embed_in_place, embed_in_place_supported,
+                            _reads_in_place)
 from .image import (_KernelApply, kernel_apply, chain_kernel_apply, _Recombine, recombine, _image_loss_raw, _L1Mean, l1_mean,  # noqa: E402,F401
                     image_metrics, relative_mse, LOSS2_KINDS, _ImageLoss2, image_loss2, image_eval)
 from .splat import (SPLAT_SOFTMAX, SPLAT_SHIFT, _splat_dims, _KernelSplat, kernel_splat, logit_max)  # noqa: E402,F401

@@ -7,7 +7,7 @@ from .. import ops as _sw          # the package itself: switches and rebound st
 from .._lib import check, lib
 from ._base import _Timed, _as_nhwc_nograd, _need_cuda, _ptr, _stream, _v, as_nhwc, is_nhwc_view, nhwc_empty, to_nhwc_raw
 from .conv_split import (_CatBroadcastChainX, _CatUpsampleChainX, _ChainSppMeanX, _pack_chain_x, _split_shared,
-                         conv_chain)
+                         conv_chain, presplit_shared, split_from_nchw_raw)
 from .elementwise import cat_broadcast, spp_mean, upsample2
 from .grads import _sink
 
@@ -21,15 +21,44 @@ def _dense_pixel_stride(g):
     return None
 
 
+def embed_in_place_supported(x, widths=(64, 64, 64)):
+    """True when the fused embedding chain (layer widths ``widths``) will read the channel-first fp32 tensor `x` where it lies
+    (``wcmc_embed3_*_nchw``): the switches, the mode, the chain's channel counts and ``wcmc_embed3_nchw_supported`` on x's shape
+    and strides.  Launches nothing and needs no device."""
+    if not (_sw.EMBED_IN_PLACE and _sw.FUSE_EMBED and _sw.DEBUG_ACTS is None and _sw.reduced_backward()):
+        return False
+    if x.dim() != 4 or x.dtype != torch.float32 or x.requires_grad or x.data_ptr() % 4:
+        return False
+    n, c, h, w = x.shape
+    return bool(lib().wcmc_embed3_supported(c, *widths) and lib().wcmc_embed3_nchw_supported(c, n, h, w, *x.stride()))
+
+
+def embed_in_place(x, widths=(64, 64, 64)):
+    """Tag the channel-first tensor `x` so that ``conv_chain_spp_mean(x, ...)`` reads it in place -- the counterpart of
+    ``presplit_shared``, which it falls back on where ``embed_in_place_supported`` says no.  Returns x."""
+    if embed_in_place_supported(x, widths):
+        x._wcmc_in_place = x._version
+        return x
+    return presplit_shared(x)
+
+
+def _reads_in_place(x):
+    """`x` carries a valid in-place tag (and no split copy, which would be read instead)."""
+    return (_sw.EMBED_IN_PLACE and getattr(x, "_wcmc_in_place", None) == x._version and getattr(x, "_wcmc_split", None) is None
+            and embed_in_place_supported(x))
+
+
 class _EmbedSppMeanFusedX(torch.autograd.Function):
     """``y = chain3(x); m = y.view(B,S,...).mean(1)`` (networks.py:33-36) with the three 1x1 layers in ONE launch
     (``wcmc_embed3_fwd``) and a backward that recomputes the hidden activations (``wcmc_embed3_bwd``): nothing but x, y and
-    the two gradients of y ever touches HBM."""
+    the two gradients of y ever touches HBM.  x: an NHWC view or a tensor with its split attached (``_split_shared``), or a
+    channel-first tensor tagged by ``embed_in_place``, which both launches read where it lies (``wcmc_embed3_*_nchw``)."""
 
     @staticmethod
     def forward(ctx, x, s, *params):
         _need_cuda(x, *params)
-        xs = _split_shared(x)
+        in_place = _reads_in_place(x)
+        xs = x.detach() if in_place else _split_shared(x)
         n, cin, h, w = x.shape
         ws_ = [params[0], params[2], params[4]]
         packs = _pack_chain_x(ws_, 1)                        # [(forward, data-gradient orientation)] per layer
@@ -37,7 +66,11 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
         m = nhwc_empty(n // s, 64, h, w, y.device)
         wb = (_ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), _ptr(packs[2][0]),
               _ptr(params[5].detach()))
-        if lib().wcmc_embed3_mean_supported(s, h * w):
+        if in_place:            # (HW % 64 == 0: the mean always leaves with y)
+            with _Timed("embed3_fwd", 4.0 * n * h * w * (cin + 64 + 64 // s), "byte"):
+                check(lib().wcmc_embed3_mean_fwd_nchw(_ptr(xs), xs.stride(0), xs.stride(1), n * h * w, cin, *wb, _ptr(y), _ptr(m), s, h * w,
+                                                      _stream()), "embed3_mean_fwd_nchw")
+        elif lib().wcmc_embed3_mean_supported(s, h * w):
             # the mean leaves with y (the kernel walks the S samples of a pixel tile and keeps their sum in registers)
             with _Timed("embed3_fwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64 + 64 // s), "byte"):
                 check(lib().wcmc_embed3_mean_fwd(_ptr(xs), n * h * w, cin, *wb, _ptr(y), _ptr(m), s, h * w, _stream()), "embed3_mean_fwd")
@@ -45,7 +78,7 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
             with _Timed("embed3_fwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64), "byte"):
                 check(lib().wcmc_embed3_fwd(_ptr(xs), n * h * w, cin, *wb, _ptr(y), _stream()), "embed3_fwd")
             check(lib().wcmc_spp_reduce(*_v(y), *_v(m), n // s, s, h, w, 64, 1.0 / s, _stream()), "spp_reduce")
-        ctx.s, ctx.dims = s, (n, cin, h, w)
+        ctx.s, ctx.dims, ctx.in_place = s, (n, cin, h, w), in_place
         ctx.packs = packs
         ctx.save_for_backward(xs, *params)
         return y, m
@@ -67,12 +100,15 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
         nb = lib().wcmc_embed3_bwd_workspace_bytes()
         ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         packs = ctx.packs
-        with _Timed("embed3_bwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64 + (64 // s if gm is not None else 0)), "byte"):
-            check(lib().wcmc_embed3_bwd(_ptr(xs), n * h * w, cin, _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1),
-                                        _ptr(packs[1][1]), _ptr(packs[2][1]), _ptr(gy), _dense_pixel_stride(gy) if gy is not None else 0,
-                                        _ptr(gm), _dense_pixel_stride(gm) if gm is not None else 0, s, h * w, 1.0 / s,
-                                        _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nb, _stream()),
-                  "embed3_bwd")
+        rest = (n * h * w, cin, _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), _ptr(packs[1][1]), _ptr(packs[2][1]),
+                _ptr(gy), _dense_pixel_stride(gy) if gy is not None else 0, _ptr(gm), _dense_pixel_stride(gm) if gm is not None else 0,
+                s, h * w, 1.0 / s, _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nb, _stream())
+        if ctx.in_place:
+            with _Timed("embed3_bwd", 4.0 * n * h * w * (cin + 64 + (64 // s if gm is not None else 0)), "byte"):
+                check(lib().wcmc_embed3_bwd_nchw(_ptr(xs), xs.stride(0), xs.stride(1), *rest), "embed3_bwd_nchw")
+        else:
+            with _Timed("embed3_bwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64 + (64 // s if gm is not None else 0)), "byte"):
+                check(lib().wcmc_embed3_bwd(_ptr(xs), *rest), "embed3_bwd")
         return (None, None, dw0, db0, dw1, db1, dw2, db2)
 
 
@@ -159,10 +195,16 @@ def conv_chain_spp_mean(x, s, ksize, pad, acts, params):
         elif not lib().wcmc_embed3_supported(params[0].shape[1], params[0].shape[0], params[2].shape[0], params[4].shape[0]):
             _note_unfused("PathNet.embedding", "channels %d -> %d -> %d -> %d" % (params[0].shape[1], params[0].shape[0],
                                                                                  params[2].shape[0], params[4].shape[0]))
-        elif getattr(x, "_wcmc_split", None) is not None or is_nhwc_view(x):
+        elif getattr(x, "_wcmc_split", None) is not None or is_nhwc_view(x) or _reads_in_place(x):
             return _EmbedSppMeanFusedX.apply(x, s, *params)
     if _sw.split_path() and acts[-1] == "linear":
         pre = getattr(x, "_wcmc_split", None)
+        if (pre is None and getattr(x, "_wcmc_in_place", None) == x._version and not x.requires_grad and x.is_cuda
+                and x.shape[1] <= 64 and x.shape[0] * x.shape[2] <= 65535):
+            # tagged for in-place reading, but the layer-by-layer chain is the one that runs (a switch or the mode changed since):
+            # its split is made now, for this call and this stream alone
+            x = x.detach()
+            x._wcmc_split = pre = ((x._version, None), split_from_nchw_raw(x))
         if pre is not None and pre[0] == (x._version, None) and not x.requires_grad:
             return _ChainSppMeanX.apply(x, s, (ksize, pad, tuple(acts)), *params)      # channel-first x, split attached
         return _ChainSppMeanX.apply(as_nhwc(x), s, (ksize, pad, tuple(acts)), *params)

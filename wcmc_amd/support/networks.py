@@ -33,15 +33,32 @@ class PathNet(nn.Module):
     def __str__(self):
         return "PathNet i{}in{}o{}".format(self.ic, self.intermc, self.outc)
 
-    @staticmethod
-    def _paths_nhwc(samples):
-        """Both backbones read the same ``paths`` (interfaces.py:195-196): convert it once."""
+    def _paths_in_place(self, paths):
+        """The (B*S, nf, H, W) view of ``paths`` that the fused embedding reads where it lies (``ops.embed_in_place_supported``),
+        or None.  Launches nothing either way (``graph.py`` asks before it captures a head for the conversion)."""
+        if paths.requires_grad or not paths.is_cuda or not ops.split_path():
+            return None
+        bs, spp, nf, h, w = paths.shape
+        try:
+            flat = paths.view(bs * spp, nf, h, w)
+        except RuntimeError:                    # (no such view: reshape would copy)
+            return None
+        return flat if ops.embed_in_place_supported(flat, (self.intermc,) * 3) else None
+
+    def _paths_nhwc(self, samples):
+        """Both backbones read the same ``paths`` (interfaces.py:195-196): convert it once -- or not at all, where the embedding
+        reads it in place."""
         paths = samples["paths"]
         key = (paths.data_ptr(), paths._version, tuple(paths.shape))
         cached = samples.get("_wcmc_paths_nhwc")
         if cached is not None and cached[0] == key:
             return cached[1]
         bs, spp, nf, h, w = paths.shape
+        flat = self._paths_in_place(paths)
+        if flat is not None:
+            flat = ops.embed_in_place(flat.detach(), (self.intermc,) * 3)
+            samples["_wcmc_paths_nhwc"] = (key, flat)
+            return flat
         flat = paths.reshape(bs * spp, nf, h, w)
         if (ops.split_path() and not paths.requires_grad and nf <= 64 and paths.is_cuda
                 and bs * spp * h <= 65535):
