@@ -660,7 +660,8 @@ int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float
  *   columns 20:23 of _preprocess_sbmc, :363-485) * 0.5 + 0.5; mat = (diffuse + 4 glossy + 2 specular) / 7 from the sample means of
  *   bits 2, 3, 4 of raw channel 24 + 6*(max_depth+1) (idx_sbmc['bounce_types'] :249-255, bounce 0: the p-buffer's columns 48, 54, 60).
  *   H and W must exceed patch.
- * wcmc_sanitize: x[i] <- 1e38 where x[i] is NaN, +-Inf or >= 1e38 (:623-624), in place. */
+ * wcmc_sanitize: x[i] <- 1e38 where x[i] is NaN, +-Inf or >= 1e38 (:623-624), in place; n = 0 is no work
+ *   and no error (x may then be null: an empty tensor has no storage). */
 int wcmc_reflect_index(int i, int n);
 size_t wcmc_importance_map_workspace_bytes(int H, int W, int C);
 int wcmc_importance_map(const float* img, int H, int W, int C, float* out, void* workspace, size_t workspace_bytes,

@@ -51,6 +51,10 @@ LOG_ULPS of the logarithm and 1 ulp of the division relative to the result;  bou
 these are ulp counts, not first-order sums.
 
 ``gradients`` is one fp32 subtraction of fp32 values: restated in fp32, compared bit for bit.
+
+SBMC (csrc/sbmc_data.hip: wcmc_preprocess_sbmc; the yardstick of tests/test_gpu_sbmc_edges.py), per sample and channel: ``sbmc``
+below -- bound 0 on every copied, clamped or bit-derived channel, the LLPM rule on the three log groups (its docstring); raw channel
+map: subpixel 0:2, radiance 2:5, diffuse 5:8, g-buffer 8:24, probabilities 24 (4d), light directions 24+4d (2d), bounce types 24+6d (d).
 """
 import numpy as np
 import torch
@@ -246,6 +250,56 @@ def llpm(raw, max_depth=5, shift=0):
     return llpm_tail(np.asarray(raw), max_depth, first=0, shift=shift)
 
 
+SB_S = 27
+
+
+def sbmc_split(max_depth=5):
+    """The exact (copied, clamped, bit-derived) and the log channels of sbmc_s (27) and sbmc_p (11 d), as boolean masks."""
+    d = max_depth + 1
+    log_s, log_p = np.zeros(SB_S, dtype=bool), np.zeros(11 * d, dtype=bool)
+    log_s[3:9], log_p[:4 * d] = True, True
+    return log_s, log_p
+
+
+def bounce_code(v):
+    """astype(int16) of a bounce code where int16 holds the value truncated toward zero; 0 (no tags) otherwise."""
+    t = np.trunc(np.asarray(v, dtype=np.float64))
+    return np.where((t >= -32768) & (t <= 32767), t, 0.0).astype(np.int64)
+
+
+def sbmc(raw, max_depth=5, shift=0):
+    """raw (..., C >= 24 + 7 d) fp32, the channels _preprocess_sbmc reads (subpixel 0:2, radiance 2:5, diffuse 5:8, g-buffer 8:24,
+    probabilities 24:24+4d, light directions 24+4d:24+6d, bounce types 24+6d:24+7d) -> (want_s (..., 27), want_p (..., 11 d),
+    bound_s, bound_p) in fp64.  bound = 0 on every copied, clamped or bit-derived channel.  The log groups follow llpm_tail's
+    rule -- U / k for each rounded operation in front of the logarithm (relative U of the argument is absolute U of the logarithm),
+    LOG_ULPS of logf and 1 ulp of the division relative to the result:
+        log(1 + max(total, 0)) / 10                        one addition:                      U / 10 + (LOG_ULPS + 1) ULP |v|
+        log(1 + max(max(total, 0) - max(diffuse, 0), 0)) / 10   a subtraction (|its error| <= U |difference| <= U (1 + difference))
+                                                           and an addition:                 2 U / 10 + (LOG_ULPS + 1) ULP |v|
+        log(max(prob, 0) + 1e-5) / 30                      one addition:                      U / 30 + (LOG_ULPS + 1) ULP |v|
+    shift = 1: the WRONG variant with the channels from the probabilities on read one further up."""
+    raw = np.asarray(raw)
+    d = max_depth + 1
+    assert raw.shape[-1] >= 24 + 7 * d + shift
+    x = lambda a, b: raw[..., a:b].astype(np.float64)          # noqa: E731
+    p0 = 24 + shift
+    with np.errstate(all="ignore"):
+        total, dif = np.maximum(x(2, 5), 0), np.maximum(x(5, 8), 0)
+        lt = np.log(1 + total) / 10.0
+        ls = np.log(1 + np.maximum(total - dif, 0)) / 10.0
+        want_s = np.concatenate([total, lt, ls, x(0, 2), x(8, 24)], -1)
+        bound_s = np.zeros_like(want_s)
+        bound_s[..., 3:6] = U / 10.0 + (LOG_ULPS + 1) * ULP * np.abs(lt) + ETA
+        bound_s[..., 6:9] = 2 * U / 10.0 + (LOG_ULPS + 1) * ULP * np.abs(ls) + ETA
+        lp = np.log(np.maximum(x(p0, p0 + 4 * d), 0) + float(np.float32(1e-5))) / 30.0
+        code = bounce_code(raw[..., p0 + 6 * d:p0 + 7 * d])
+        tags = [((code >> k) & 1).astype(np.float64) for k in range(5)]
+        want_p = np.concatenate([lp, np.clip(x(p0 + 4 * d, p0 + 6 * d), -1.0, 1.0)] + tags, -1)
+        bound_p = np.zeros_like(want_p)
+        bound_p[..., :4 * d] = U / 30.0 + (LOG_ULPS + 1) * ULP * np.abs(lp) + ETA
+    return want_s, want_p, bound_s, bound_p
+
+
 def gradients(buf, forward=False):
     """(h, w, c) fp32 -> (h, w, 2c) fp32: one fp32 subtraction per element, zero first column / row -- compared bit for bit."""
     buf = np.asarray(buf, dtype=np.float32)
@@ -378,6 +432,51 @@ def make_frame(h, w, s, max_depth=5, C=None, seed=0, fill="kpcn", device="cpu", 
         x[..., m["rough"]:m["rough"] + d] = rand(*n, d)
     else:
         raise ValueError(fill)
+    return x
+
+
+# The value edges of _preprocess_sbmc, one set per planted record.  bounce: codes cycled over the d bounce channels --
+# truncation toward zero of non-integer and negative codes, the int16 boundaries (-32768 and 32767.x are held, +-32768.x and
+# beyond are not), the 1e38 of sanitising; rad / dif: radiance and diffuse (total < diffuse: log 1 = 0; equal: exactly 0);
+# prob: a non-positive probability is log(1e-5) / 30; light: directions exactly at and one ulp past +-1.
+_ONE_UP = float(np.nextafter(np.float32(1), np.float32(2)))
+SBMC_EDGES = (
+    dict(bounce=(5.9, -3.0, 32767.5, -32768.0), rad=0.5, dif=2.0, prob=0.0, light=(1.0, -1.0)),
+    dict(bounce=(1e38, -32768.5, 32768.5, -1e38), rad=-1.0, dif=3.0, prob=-0.25, light=(-1.0, 1.0)),
+    dict(bounce=(-0.9, 31.999, -5.5, 32767.0), rad=1.75, dif=1.75, prob=1e-5, light=(_ONE_UP, -_ONE_UP)),
+    dict(bounce=(-32767.5, 32768.0, -32769.0, 0.5), rad=0.0, dif=-2.0, prob=-0.0, light=(0.0, -0.0)),
+)
+
+
+def sbmc_edge_records(n):
+    """The planted records of make_sbmc_frame: 0, the tile edges 127 / 128 (SB_TILE = 128), n - 1 and their neighbours."""
+    return sorted({r for r in (0, 1, 2, 3, 126, 127, 128, 129, n - 2, n - 1) if 0 <= r < n})
+
+
+def make_sbmc_frame(n, max_depth=5, C=None, seed=0, device="cpu"):
+    """Raw renderer output of n records as (n, 1, 1, C), made from a seed on ``device``: what _preprocess_sbmc reads (channels
+    [0, 24 + 7 d)) on both sides of every clamp, every channel above (which it must not read) NaN.  Record sbmc_edge_records(n)[i]
+    holds SBMC_EDGES[i % 4] in every channel of the group."""
+    C = min_channels(max_depth) if C is None else C
+    d = max_depth + 1
+    used = 24 + 7 * d
+    assert C >= used
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.full((n, 1, 1, C), NAN, device=device, dtype=torch.float32)
+    f = x.view(n, C)
+    f[:, 0:2] = torch.rand(n, 2, generator=g, device=device)
+    f[:, 2:8] = torch.randn(n, 6, generator=g, device=device) * 2.0
+    f[:, 8:24] = torch.randn(n, 16, generator=g, device=device)
+    prob = torch.exp(torch.randn(n, 4 * d, generator=g, device=device) * 2.0)
+    prob[torch.rand(n, 4 * d, generator=g, device=device) < 0.3] *= -1.0
+    f[:, 24:24 + 4 * d] = prob
+    f[:, 24 + 4 * d:24 + 6 * d] = torch.rand(n, 2 * d, generator=g, device=device) * 3.0 - 1.5
+    f[:, 24 + 6 * d:used] = torch.randint(0, 32, (n, d), generator=g, device=device).float()
+    for i, r in enumerate(sbmc_edge_records(n)):
+        e = SBMC_EDGES[i % len(SBMC_EDGES)]
+        f[r, 2:5], f[r, 5:8], f[r, 24:24 + 4 * d] = e["rad"], e["dif"], e["prob"]
+        f[r, 24 + 4 * d:24 + 6 * d] = torch.tensor([e["light"][k % 2] for k in range(2 * d)], device=device)
+        f[r, 24 + 6 * d:used] = torch.tensor([e["bounce"][(k + r) % 4] for k in range(d)], device=device)
     return x
 
 

@@ -397,7 +397,7 @@ extern "C" int wcmc_sampling_prob(const float* raw, const float* gt, int H, int 
 }
 
 extern "C" int wcmc_sanitize(float* x, int64_t n, void* stream) {
-  WCMC_REQUIRE(x && n >= 0, WCMC_ERR_BAD_ARG, "sanitize: null pointer or negative count");
+  WCMC_REQUIRE((x || n == 0) && n >= 0, WCMC_ERR_BAD_ARG, "sanitize: null pointer or negative count");   // (an empty tensor has no storage)
   if (n == 0) return WCMC_OK;
   hipLaunchKernelGGL(sm_sanitize_kernel, dim3(sm_flat_grid(n)), dim3(SM_THREADS), 0, (hipStream_t)stream, x, n);
   return check_launch("sanitize");
