@@ -825,6 +825,33 @@ int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const f
 int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S, float* out,
                              float* ipt, float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
 
+/* ---------------------------------------------------------------- dihedral self-ensemble of a frame
+ * The tile batches of the frame AS IF the raw frame had been transformed by T_t before preprocessing, and the way back.  Code t in
+ * 0..7 is that of the `_aug` patch entry points: T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) on the row and column axes;
+ * the transformed frame is H x W for even t and W x H for odd t, and its pixel (y, x) is source pixel (sy, sx) = (y, x),
+ * (x, W-1-y), (H-1-y, W-1-x), (H-1-x, y) for k = 0..3, then sx = W-1-sx if t & 4.  One code per launch; H and W are always the
+ * SOURCE buffers' sizes; origins and coords are in the TRANSFORMED frame's coordinates.  t outside 0..7 is refused on the host and
+ * masked in the kernels; every mirrored and mapped index is clamped before use.
+ * assemble_kpcn_tiles_aug: assemble_kpcn_tiles through the mirror of the transformed frame and then the map above.  Copied channels
+ *   are the source record's (direction-valued ones are not re-expressed); each of the 26 differences is
+ *   value[src(p)] - value[src(p - e)], e one step along the transformed frame's x / y, one fp32 subtraction (also of a record with
+ *   itself), and exactly 0 at the transformed extended frame's first column / row.  Bit for bit assemble_kpcn_tiles on the buffers
+ *   preprocessed from the host-transformed raw frame.  pad and P conditions as the plain entry point's, against the transformed sizes.
+ * assemble_sample_tiles_aug (csrc/sbmc_data.hip): assemble_sample_tiles through the same composed map; copies only.
+ * stitch_tiles_aug: for every tile b with coords[b] = (i_start, j_start, i_end, j_end, i, j) of the transformed frame's table (device
+ *   int32 (B, 6)) and every pixel (y, x) of its owned window, v = rad (B, 3, ho, wo) 'replicate'-padded back to P x P as stitch_tiles
+ *   does it, and out_rad[:, sy, sx] = v (accumulate = 0) or out_rad[:, sy, sx] + v (accumulate = 1); out_rad (3, H, W) contiguous, in
+ *   SOURCE orientation.  The owned windows partition the frame, so a launch set touches every element once: no atomics, and passes
+ *   that follow one another on one stream give a bit-defined sum.  No P-buffers (those are the identity pass's). */
+int wcmc_assemble_kpcn_tiles_aug(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P, int pad,
+                                 int t, float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer,
+                                 float* albedo, float* paths, void* stream);
+int wcmc_assemble_sample_tiles_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B, int H,
+                                   int W, int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf, float* radiance,
+                                   float* features, float* paths, void* stream);
+int wcmc_stitch_tiles_aug(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,
+                          const int* coords, int B, int t, int H, int W, int accumulate, float* out_rad, void* stream);
+
 /* ---------------------------------------------------------------- filtering a frame by its P-buffer (csrc/pbuffer_filter.hip)
  * Non-local means whose patch distance is taken between the per-pixel statistics of the path embedding (Ray Histogram Fusion with
  * the learned manifold in place of the colour histograms).  The build's own specification: DESIGN.md section 19.

@@ -144,6 +144,9 @@ SIGNATURES = {
     "wcmc_finish_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
     "wcmc_assemble_sample_tiles": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P]),
     "wcmc_finish_sample_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
+    "wcmc_assemble_kpcn_tiles_aug": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P]),
+    "wcmc_assemble_sample_tiles_aug": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
+    "wcmc_stitch_tiles_aug": (I, [P, L, L, L, L, I, I, I, P, I, I, I, I, I, P, P]),
     "wcmc_pbuffer_filter_workspace_bytes": (Z, [I, I, I, I]),
     "wcmc_pbuffer_filter": (I, [P, L, L, L, P, L, L, L, L, P, I, P, P, P, Z, I, I, I, I, I, I, I, F, F, I, P]),
 }

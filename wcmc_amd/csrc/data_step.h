@@ -151,6 +151,22 @@ __device__ __forceinline__ PatchMap patch_map(int t, int y, int x, int P) {
   return m;
 }
 
+// Whole-frame dihedral transforms (the self-ensemble of wcmc_amd.denoise): patch_map with the H x W frame's
+// own two sizes in place of P.  T_t of the frame is H x W for even t and W x H for odd t; (y, x) is a position INSIDE the transformed
+// frame (mirrored already), and the result the source pixel of the stored H x W buffers.  The code is masked to 0..7; the result is
+// clamped, so a position the host check let through cannot lead outside the buffers.
+struct FramePos { int sy, sx; };
+__device__ __forceinline__ FramePos frame_map(int t, int y, int x, int H, int W) {
+  const int k = t & 3;
+  FramePos m;
+  m.sy = k == 0 ? y : k == 1 ? x : k == 2 ? H - 1 - y : H - 1 - x;
+  m.sx = k == 0 ? x : k == 1 ? W - 1 - y : k == 2 ? W - 1 - x : y;
+  if (t & 4) m.sx = W - 1 - m.sx;
+  m.sy = min(max(m.sy, 0), H - 1);
+  m.sx = min(max(m.sx, 0), W - 1);
+  return m;
+}
+
 // Launchers of the patch-assembly kernels (preprocess.hip, sbmc_data.hip).  The per-sample buffers hold S_total samples per pixel,
 // the outputs the first s of them; the arguments have been validated by the entry point that calls.  transforms: null launches the
 // plain kernel; B device ints launch the instantiation that applies patch_map (the `_aug` entry points).

@@ -7,6 +7,9 @@
 //                             (data_step.h: pp_kpcn_finish) are taken again from the stored values wherever a neighbour lies across
 //                             the edge.  Bit for bit what preprocessing the padded raw frame and wcmc_assemble_kpcn_patches give.
 //   wcmc_finish_frame         one pass over the stitched frame: the noisy input, the has-hit mask, the composite and 8-bit previews.
+// The dihedral self-ensemble adds the way through a whole-frame transform and back:
+//   wcmc_assemble_kpcn_tiles_aug  the same batch of the frame as if the RAW frame had been flipped / turned before preprocessing.
+//   wcmc_stitch_tiles_aug         pastes or adds the owned windows of the transformed frame's tiles into the frame in source orientation.
 #include "data_step.h"
 
 namespace wcmc {
@@ -18,43 +21,72 @@ struct TileOut {
 // (ft_grad_src / ft_grad_dst, the channels of the backward differences, are in data_step.h: the augmented patch assembler uses them too)
 // One thread per (tile, y, x), as pp_assemble_kpcn_kernel: every output plane is written as coalesced rows, each record is read once
 // (a second record's thirteen values only where a difference crosses the frame's edge: the outer `pad` ring of border tiles).
-template <bool VEC>
+// AUG (the `_aug` entry point): the whole launch reads the frame through one dihedral transform t.  The origins
+// and the mirror are those of the TRANSFORMED frame (Ht x Wt: W x H for odd t), frame_map then gives the source record, and each of the
+// 26 differences is value[src(p)] - value[src(p - e)] with e one step along the transformed frame's x / y.  Where that neighbour's
+// source is the stored one (one column / row before the source) the stored difference is that very subtraction and is kept; elsewhere
+// thirteen floats of the neighbour's record are read.  AUG = false is the plain kernel: its body is the one it had.
+template <bool VEC, bool AUG>
 __global__ __launch_bounds__(256) void ft_assemble_tiles_kernel(const float* __restrict__ kpcn, const float* __restrict__ llpm,
                                                                 const int* __restrict__ origins, TileOut o, int B, int H, int W,
-                                                                int S, int P, int pad) {
+                                                                int S, int P, int pad, int t) {
   const int64_t total = (int64_t)B * P * P;
   const int cin = llpm ? 35 : 34;
   const int64_t plane = (int64_t)P * P;
+  const int Ht = AUG && (t & 1) ? W : H, Wt = AUG && (t & 1) ? H : W;         // the transformed frame's sizes
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % P), y = (int)((i / P) % P), b = (int)(i / plane);
     const int r = origins[2 * b] + y, c = origins[2 * b + 1] + x;             // (row, column) of the frame; may lie outside
-    const int mr = ft_mirror(r, H), mc = ft_mirror(c, W);
-    const int64_t pix = (int64_t)mr * W + mc;
+    const int mr = ft_mirror(r, Ht), mc = ft_mirror(c, Wt);
+    FramePos sp{mr, mc};
+    if (AUG) sp = frame_map(t, mr, mc, H, W);
+    const int64_t pix = (int64_t)sp.sy * W + sp.sx;
     const float* k = kpcn + pix * KP_C;
     float v[KP_C];
     if (VEC) {
 #pragma unroll
       for (int q = 0; q < KP_C / 4; ++q) {
-        const float4 t = *reinterpret_cast<const float4*>(k + 4 * q);
-        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        const float4 f = *reinterpret_cast<const float4*>(k + 4 * q);
+        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
       }
     } else {
 #pragma unroll
       for (int ch = 0; ch < KP_C; ++ch) v[ch] = k[ch];
     }
-    // The stored difference is that of the extended frame only where both operands are in-frame neighbours (1 <= c < W); elsewhere
-    // it is value[m(r), m(c)] - value[m(r), m(c - 1)], and 0 in the extended frame's first column / row (frame position -pad).
-    if (c < 1 || c >= W) {
-      const bool first = c + pad <= 0;
-      const float* kl = kpcn + ((int64_t)mr * W + ft_mirror(c - 1, W)) * KP_C;
+    if (AUG) {
+      {
+        const bool first = c + pad <= 0;
+        const FramePos n = frame_map(t, mr, ft_mirror(c - 1, Wt), H, W);      // source of the left neighbour in the transformed frame
+        if (first || n.sy != sp.sy || n.sx != sp.sx - 1) {
+          const float* kl = kpcn + ((int64_t)n.sy * W + n.sx) * KP_C;
 #pragma unroll
-      for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, false)] = first ? 0.f : v[ft_grad_src(g)] - kl[ft_grad_src(g)];
-    }
-    if (r < 1 || r >= H) {
-      const bool first = r + pad <= 0;
-      const float* ku = kpcn + ((int64_t)ft_mirror(r - 1, H) * W + mc) * KP_C;
+          for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, false)] = first ? 0.f : v[ft_grad_src(g)] - kl[ft_grad_src(g)];
+        }
+      }
+      {
+        const bool first = r + pad <= 0;
+        const FramePos n = frame_map(t, ft_mirror(r - 1, Ht), mc, H, W);      // ... of the upper neighbour
+        if (first || n.sx != sp.sx || n.sy != sp.sy - 1) {
+          const float* ku = kpcn + ((int64_t)n.sy * W + n.sx) * KP_C;
 #pragma unroll
-      for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, true)] = first ? 0.f : v[ft_grad_src(g)] - ku[ft_grad_src(g)];
+          for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, true)] = first ? 0.f : v[ft_grad_src(g)] - ku[ft_grad_src(g)];
+        }
+      }
+    } else {
+      // The stored difference is that of the extended frame only where both operands are in-frame neighbours (1 <= c < W); elsewhere
+      // it is value[m(r), m(c)] - value[m(r), m(c - 1)], and 0 in the extended frame's first column / row (frame position -pad).
+      if (c < 1 || c >= W) {
+        const bool first = c + pad <= 0;
+        const float* kl = kpcn + ((int64_t)mr * W + ft_mirror(c - 1, W)) * KP_C;
+#pragma unroll
+        for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, false)] = first ? 0.f : v[ft_grad_src(g)] - kl[ft_grad_src(g)];
+      }
+      if (r < 1 || r >= H) {
+        const bool first = r + pad <= 0;
+        const float* ku = kpcn + ((int64_t)ft_mirror(r - 1, H) * W + mc) * KP_C;
+#pragma unroll
+        for (int g = 0; g < KP_NV; ++g) v[ft_grad_dst(g, true)] = first ? 0.f : v[ft_grad_src(g)] - ku[ft_grad_src(g)];
+      }
     }
     const int64_t po = (int64_t)y * P + x;
     float* din = o.din + (int64_t)b * cin * plane + po;
@@ -155,6 +187,43 @@ __global__ __launch_bounds__(256) void ft_finish_sample_frame_kernel(const float
   }
 }
 
+// The way back of the self-ensemble: ie_stitch_kernel's radiance half for tiles of the frame TRANSFORMED by
+// code t, written to (or added to) the frame in SOURCE orientation.  coords: the (B, 6) table of the transformed Ht x Wt frame.  One
+// thread per (channel, owned pixel): the reads run along the network output's rows; the writes run along source rows for even t
+// and down source columns for odd t.  The owned windows partition the frame and frame_map is a bijection, so every element of
+// out_rad is touched by one thread of one launch of a pass: `out + v` needs no atomic and is the same bits on every run.
+struct StitchAugArgs {
+  const float* rad; int64_t rsb, rsc, rsh, rsw;     // (B, 3, ho, wo) network output
+  const int* coords;                                // (B, 6): i_start, j_start, i_end, j_end, i, j of the transformed frame
+  float* orad;                                      // (3, H, W), source orientation
+  int ho, wo, P, H, W, t;
+};
+
+template <bool ACC>
+__global__ __launch_bounds__(256) void ft_stitch_aug_kernel(StitchAugArgs a) {
+  const int b = blockIdx.y;
+  const int* cd = a.coords + 6 * b;
+  const int i0 = cd[0], j0 = cd[1], i1 = cd[2], j1 = cd[3], ib = cd[4], jb = cd[5];
+  const int Ht = a.t & 1 ? a.W : a.H, Wt = a.t & 1 ? a.H : a.W;
+  // a window outside the transformed frame or the tile is skipped (the wrapper validates the table on the host before upload)
+  if (i0 < 0 || j0 < 0 || i1 > Ht || j1 > Wt || i0 >= i1 || j0 >= j1 || i0 < ib || j0 < jb || i1 > ib + a.P || j1 > jb + a.P)
+    return;
+  const int wh = i1 - i0, ww = j1 - j0;
+  const int64_t win = (int64_t)wh * ww;
+  const int top = (a.P - a.ho) / 2, left = (a.P - a.wo) / 2;      // the 'replicate' padding of ie_stitch_kernel
+  const int64_t hw = (int64_t)a.H * a.W;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < 3 * win; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t plane = e / win, q = e - plane * win;
+    const int dy = (int)(q / ww), dx = (int)(q - (int64_t)dy * ww);
+    const int y = i0 + dy, x = j0 + dx;                           // pixel of the transformed frame
+    const int sy = min(max(y - ib - top, 0), a.ho - 1), sx = min(max(x - jb - left, 0), a.wo - 1);
+    const float v = a.rad[b * a.rsb + plane * a.rsc + sy * a.rsh + sx * a.rsw];
+    const FramePos p = frame_map(a.t, y, x, a.H, a.W);
+    float* dst = a.orad + plane * hw + (int64_t)p.sy * a.W + p.sx;
+    *dst = ACC ? *dst + v : v;
+  }
+}
+
 }  // namespace wcmc
 
 using namespace wcmc;
@@ -188,12 +257,58 @@ extern "C" int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, co
   const int64_t total = (int64_t)B * P * P;
   const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
   if (aligned16(kpcn))
-    hipLaunchKernelGGL(ft_assemble_tiles_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B, H,
-                       W, S, P, pad);
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
+                       B, H, W, S, P, pad, 0);
   else
-    hipLaunchKernelGGL(ft_assemble_tiles_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B, H,
-                       W, S, P, pad);
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
+                       B, H, W, S, P, pad, 0);
   return check_launch("assemble_kpcn_tiles");
+}
+
+extern "C" int wcmc_assemble_kpcn_tiles_aug(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P,
+                                            int pad, int t, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+                                            float* specular_buffer, float* albedo, float* paths, void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: the transform code must lie in 0..7 (got %d)", t);
+  WCMC_REQUIRE(kpcn && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles_aug: null pointer");
+  WCMC_REQUIRE(!llpm || (paths && S > 0), WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: llpm needs a paths output and S > 0");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles_aug: B, H, W, P must be positive and pad non-negative");
+  const int Ht = t & 1 ? W : H, Wt = t & 1 ? H : W;
+  WCMC_REQUIRE(pad < Ht && pad < Wt, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles_aug: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+  WCMC_REQUIRE(P <= Ht + 2 * pad && P <= Wt + 2 * pad, WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_tiles_aug: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
+  TileOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths};
+  const int64_t total = (int64_t)B * P * P;
+  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+  if (aligned16(kpcn))
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B,
+                       H, W, S, P, pad, t);
+  else
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
+                       B, H, W, S, P, pad, t);
+  return check_launch("assemble_kpcn_tiles_aug");
+}
+
+extern "C" int wcmc_stitch_tiles_aug(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,
+                                     const int* coords, int B, int t, int H, int W, int accumulate, float* out_rad, void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "stitch_tiles_aug: the transform code must lie in 0..7 (got %d)", t);
+  WCMC_REQUIRE(rad && coords && out_rad, WCMC_ERR_BAD_ARG, "stitch_tiles_aug: null pointer");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "stitch_tiles_aug: B, H, W, P must be positive");
+  WCMC_REQUIRE((ho == P && wo == P) || (ho > 0 && wo > 0 && ho < P && wo < P), WCMC_ERR_BAD_ARG,
+               "stitch_tiles_aug: the %d x %d network output must be P x P or smaller in both dimensions (P = %d)", ho, wo, P);
+  WCMC_REQUIRE(accumulate == 0 || accumulate == 1, WCMC_ERR_BAD_ARG, "stitch_tiles_aug: accumulate must be 0 or 1 (got %d)",
+               accumulate);
+  WCMC_REQUIRE(B <= 65535, WCMC_ERR_BAD_ARG, "stitch_tiles_aug: at most 65535 tiles per launch");
+  StitchAugArgs a{rad, rsb, rsc, rsh, rsw, coords, out_rad, ho, wo, P, H, W, t};
+  const int64_t bx = ((int64_t)P * P * 3 + 255) / 256;
+  if (accumulate)
+    hipLaunchKernelGGL(ft_stitch_aug_kernel<true>, dim3((unsigned)(bx < 1024 ? bx : 1024), B), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(ft_stitch_aug_kernel<false>, dim3((unsigned)(bx < 1024 ? bx : 1024), B), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("stitch_tiles_aug");
 }
 
 extern "C" int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm, int H, int W, int S, float* out,

@@ -194,8 +194,13 @@ int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* ll
 // frame edge runs backwards on the far side of it).  All three buffers are per sample, so a mirrored position is a copy of its
 // image's record -- nothing is recomputed -- and there is no gt source.  LDS tile and write pattern as above; the reads run along c
 // too, a pixel per half-wave.
+// AUG (the `_aug` entry point): the whole launch reads the frame through one dihedral transform `code`.
+// Origins and mirror are those of the TRANSFORMED frame (Ht x Wt: W x H for odd codes) and frame_map gives each of the chunk's 32
+// pixels its source record: along a source row for even codes, down a source column for odd ones.  Every channel is a copy; the
+// LDS tile and the writes are unchanged.
+template <bool AUG>
 __global__ __launch_bounds__(256) void sa_assemble_tiles_kernel(SampleBatch a, const int* __restrict__ origins, int64_t units, int H,
-                                                                int W, int P) {
+                                                                int W, int P, int code) {
   extern __shared__ __attribute__((aligned(16))) float sa_tile[];
   const int nxc = (P + SA_XT - 1) / SA_XT;
   const int64_t plane = (int64_t)P * P;
@@ -211,14 +216,21 @@ __global__ __launch_bounds__(256) void sa_assemble_tiles_kernel(SampleBatch a, c
     const int x0 = xc * SA_XT, xcnt = min(SA_XT, P - x0);
     const int s0 = sc * SA_SC, scnt = min(SA_SC, sr.S - s0);
     // (the host checks the origins; ft_mirror's clamp keeps a bad one from reading outside the buffers)
-    const int r = ft_mirror(origins[2 * b] + y, H), c = origins[2 * b + 1] + x0;
+    const int Ht = AUG && (code & 1) ? W : H, Wt = AUG && (code & 1) ? H : W; // the transformed frame's sizes
+    const int r = ft_mirror(origins[2 * b] + y, Ht), c = origins[2 * b + 1] + x0;
     const int run = scnt * sr.C, LD = (SA_SC * sr.C) | 1;
     const int64_t pitch = (int64_t)sr.Sp * sr.C;
-    const float* base = sr.p + (int64_t)r * W * pitch + (int64_t)s0 * sr.C;
+    const float* base = sr.p + (AUG ? 0 : (int64_t)r * W * pitch) + (int64_t)s0 * sr.C;
     // eight pixels at a time, 32 lanes along each pixel's run (128-byte segments): the source column is mirrored once per pixel,
     // not once per float, and no index is divided
     for (int px = threadIdx.x >> 5; px < xcnt; px += 8) {
-      const float* src = base + ft_mirror(c + px, W) * pitch;
+      const float* src;
+      if (AUG) {
+        const FramePos sp = frame_map(code, r, ft_mirror(c + px, Wt), H, W);
+        src = base + ((int64_t)sp.sy * W + sp.sx) * pitch;
+      } else {
+        src = base + ft_mirror(c + px, W) * pitch;
+      }
       float* dst = sa_tile + px * LD;
 #pragma unroll 4
       for (int e = threadIdx.x & 31; e < run; e += 32) dst[e] = src[e];
@@ -240,20 +252,9 @@ __global__ __launch_bounds__(256) void sa_assemble_tiles_kernel(SampleBatch a, c
 
 using namespace wcmc;
 
-extern "C" int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
-                                          int H, int W, int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance,
-                                          float* features, float* paths, void* stream) {
-  WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: null pointer");
-  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: use_sbmc_buf needs sbmc_p");
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: llpm needs a paths output");
-  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles: B, H, W, P must be positive and pad non-negative");
-  WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: S must be positive (got %d)", S);
-  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
-  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
-  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
+// the three sources and the work units of a tile launch (both entry points below)
+static SampleBatch sa_tile_batch(const float* sbmc_s, const float* sbmc_p, const float* llpm, int S, int P, int B, int use_g_buf,
+                                 int use_sbmc_buf, float* radiance, float* features, float* paths, int64_t* units_out) {
   SampleBatch a;
   a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = nullptr;
   a.ng = use_g_buf ? 24 : 3;
@@ -268,10 +269,54 @@ extern "C" int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc
     a.src[k].first = units;
     if (a.src[k].nout > 0) units += rows * ((S + SA_SC - 1) / SA_SC);
   }
+  *units_out = units;
+  return a;
+}
+
+extern "C" int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
+                                          int H, int W, int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance,
+                                          float* features, float* paths, void* stream) {
+  WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: null pointer");
+  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: use_sbmc_buf needs sbmc_p");
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: llpm needs a paths output");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: B, H, W, P must be positive and pad non-negative");
+  WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: S must be positive (got %d)", S);
+  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
+  int64_t units;
+  const SampleBatch a = sa_tile_batch(sbmc_s, sbmc_p, llpm, S, P, B, use_g_buf, use_sbmc_buf, radiance, features, paths, &units);
   const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  hipLaunchKernelGGL(sa_assemble_tiles_kernel, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, (hipStream_t)stream,
-                     a, origins, units, H, W, P);
+  hipLaunchKernelGGL(sa_assemble_tiles_kernel<false>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds,
+                     (hipStream_t)stream, a, origins, units, H, W, P, 0);
   return check_launch("assemble_sample_tiles");
+}
+
+extern "C" int wcmc_assemble_sample_tiles_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
+                                              int H, int W, int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf,
+                                              float* radiance, float* features, float* paths, void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: the transform code must lie in 0..7 (got %d)", t);
+  WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: null pointer");
+  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: use_sbmc_buf needs sbmc_p");
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: llpm needs a paths output");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles_aug: B, H, W, P must be positive and pad non-negative");
+  WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: S must be positive (got %d)", S);
+  const int Ht = t & 1 ? W : H, Wt = t & 1 ? H : W;
+  WCMC_REQUIRE(pad < Ht && pad < Wt, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles_aug: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+  WCMC_REQUIRE(P <= Ht + 2 * pad && P <= Wt + 2 * pad, WCMC_ERR_BAD_ARG,
+               "assemble_sample_tiles_aug: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
+  int64_t units;
+  const SampleBatch a = sa_tile_batch(sbmc_s, sbmc_p, llpm, S, P, B, use_g_buf, use_sbmc_buf, radiance, features, paths, &units);
+  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
+  hipLaunchKernelGGL(sa_assemble_tiles_kernel<true>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds,
+                     (hipStream_t)stream, a, origins, units, H, W, P, t);
+  return check_launch("assemble_sample_tiles_aug");
 }
 
 extern "C" int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples, int C, int max_depth, float* out_s, float* out_p,

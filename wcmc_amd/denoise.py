@@ -1,7 +1,8 @@
 """Denoise raw renders of any size with a trained KPCN, SBMC or LBMC model: no ground truth, no offline files, every pixel.
 
     python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
-        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--rhf] [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
+        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--rhf] [--self_ensemble [CODE ...]] \\
+        [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
     python -m wcmc_amd.denoise ... --model_name SBMC_manifold --denoiser my_pkg.models:make_multisteps [--use_sbmc_buf] [--tile_pad N]
 
 Per input file (renderer output (H, W, S, 104), H and W at least 64): the first ``--spp`` samples (default: what the file holds; a
@@ -12,7 +13,9 @@ memory, and the next file's bands cross while this one's network runs; ``--band_
 ``OUT/<stem>_denoised.npy`` and ``.pfm`` hold the (H, W, 3) float frame.  ``--png`` adds 8-bit tone-mapped previews of the result
 and of the noisy input, ``--save_pbuffer`` the stitched P-buffer as (H, W, S, C).  ``--rhf`` filters the noisy input by the stitched
 P-buffer (``wcmc_amd.rhf``; ``--rhf_radius``, ``--rhf_patch_radius``, ``--rhf_bandwidth``, ``--rhf_eps``) with ``has_hit`` as the mask and
-writes ``<stem>_rhf.npy`` and the neighbour count ``<stem>_rhf_neighbours.npy`` (PNGs with ``--png``).  The model flags are those of
+writes ``<stem>_rhf.npy`` and the neighbour count ``<stem>_rhf_neighbours.npy`` (PNGs with ``--png``).  ``--self_ensemble [CODE ...]``
+denoises the frame under several dihedral codes of ``--augment`` (bare: all eight; ``0 2 4 6``: the flips), turns every result back
+and averages them; the P-buffer stays the un-ensembled one.  The model flags are those of
 ``wcmc_amd.train_kpcn``; the model is ``<save>/<model_name>.pth``.  One line per frame reports the seconds of each phase.
 
 A model whose name holds ``SBMC`` / ``LBMC`` is a ``train_sbmc`` / ``train_lbmc`` checkpoint around the caller's base denoiser
@@ -176,10 +179,10 @@ def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, prepro
     if sample_launcher(args.model_name) is not None:
         res = denoise_sample_frame(interface, bufs[0], bufs[1], llpm, args.use_llpm_buf, args.use_g_buf, args.use_sbmc_buf,
                                    batch_size, want_pbuffers=want_p, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
-                                   preview=args.png, times=times)
+                                   preview=args.png, times=times, ensemble=ensemble_codes(args))
     else:
         res = denoise_frame(interface, bufs[0], llpm, args.use_llpm_buf, batch_size, want_pbuffers=want_p,
-                            patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times)
+                            patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times, ensemble=ensemble_codes(args))
     out, out_path = res[0], (res[3] if want_p else None)
     os.makedirs(output_dir, exist_ok=True)
     img = out.cpu().numpy()
@@ -285,6 +288,11 @@ def build_parser():
     p.add_argument('--rhf', action='store_true',
                    help='also filter the noisy input by the stitched P-buffer (wcmc_amd.rhf) and write <stem>_rhf.npy and the '
                         'neighbour count <stem>_rhf_neighbours.npy, PNGs with --png; needs --use_llpm_buf')
+    p.add_argument('--self_ensemble', type=int, nargs='*', default=None, metavar='CODE',
+                   help='dihedral self-ensemble: denoise the frame under several flips / quarter turns (codes 0..7 of --augment: '
+                        'rot90 by CODE & 3 after a left-right flip if CODE & 4), turn every result back and average.  Without values: '
+                        'all eight codes; `0 2 4 6` are the row-preserving codes (flips only).  The set must contain 0.  The network '
+                        'time grows with the number of codes; meant for models trained with --augment')
     rhf.add_filter_arguments(p, prefix='rhf_')
     add_sample_arguments(p)
     p.add_argument('--tile_pad', type=int, default=PAD_SIZE, metavar='N',
@@ -309,8 +317,23 @@ def add_sample_arguments(p):
     return p
 
 
+def ensemble_codes(args):
+    """The self-ensemble set of ``--self_ensemble``, checked: (0,) without the flag, all eight codes for the bare flag, else the listed
+    codes sorted.  A set without 0, a repeated code or a code outside 0..7 is a ``ValueError`` that names the flag."""
+    codes = getattr(args, 'self_ensemble', None)
+    if codes is None:
+        return (0,)
+    if len(codes) == 0:
+        return tuple(range(8))
+    try:
+        return ops.check_frame_transforms(codes)
+    except ValueError as e:
+        raise ValueError("--self_ensemble %s: %s" % (' '.join(str(c) for c in codes), str(e).split(': ', 1)[-1])) from None
+
+
 def check_inputs(args):
     """Everything that can be refused before the GPU is touched: sample counts, continuation files, the tile batch size, the band."""
+    ensemble_codes(args)
     if sample_launcher(args.model_name) is not None:
         from .train_sbmc import load_denoiser_factory
         load_denoiser_factory(getattr(args, 'denoiser', None))        # (a DenoiserFactoryError, before any file is looked for)

@@ -4,6 +4,7 @@ the buffers and batches of the sample-based denoisers (csrc/sbmc_data.hip), ever
 render of any size (csrc/frame_tiles.hip)."""
 import ctypes
 import math
+import numbers
 
 import torch
 
@@ -452,19 +453,69 @@ def check_tile_origins(origins, h, w, patch, pad, who="assemble_kpcn_tiles"):
         raise ValueError("%s: a %d-pixel tile origin lies outside the %dx%d frame extended by %d" % (who, patch, h, w, pad))
 
 
-def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=True):
+def check_frame_transforms(codes):
+    """Host check of a self-ensemble set: distinct dihedral codes in 0..7 that contain 0 (the identity pass
+    gives the P-buffers).  Returns them as a sorted tuple, the order the passes are summed in."""
+    try:
+        codes = [c for c in codes]
+    except TypeError:
+        raise ValueError("check_frame_transforms: the ensemble should be a sequence of codes 0..7, got %r" % (codes,))
+    for c in codes:
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= int(c) <= 7:
+            raise ValueError("check_frame_transforms: code %r lies outside 0..7" % (c,))
+    codes = [int(c) for c in codes]
+    if len(set(codes)) != len(codes):
+        raise ValueError("check_frame_transforms: a code is repeated in %s" % (codes,))
+    if 0 not in codes:
+        raise ValueError("check_frame_transforms: the set %s does not contain 0 (the identity pass gives the P-buffers)" % (codes,))
+    return tuple(sorted(codes))
+
+
+def _frame_transform(who, transform):
+    """One whole-frame code: None and 0 are the plain call path."""
+    if transform is None:
+        return 0
+    if isinstance(transform, bool) or not isinstance(transform, numbers.Integral) or not 0 <= int(transform) <= 7:
+        raise ValueError("%s: the transform code %r lies outside 0..7" % (who, transform))
+    return int(transform)
+
+
+def stitch_tiles_aug(out, coords, out_rad, transform, accumulate, patch=128):
+    """The way back of the self-ensemble (``wcmc_stitch_tiles_aug``): paste (``accumulate`` False) or add (True) one batch of tiles
+    of the frame transformed by code ``transform`` into ``out_rad`` (3, H, W), which stays in SOURCE orientation.  out: (B, 3, ho, wo)
+    network output, 'replicate'-padded back to ``patch`` on the fly as ``stitch_tiles`` does it; coords: device int32 (B, 6) rows of
+    the TRANSFORMED frame's table, which passed ``check_tile_coords`` against the transformed sizes.  No P-buffers."""
+    _need_cuda(out, out_rad)
+    t = _frame_transform("stitch_tiles_aug", transform)
+    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
+            and coords.is_contiguous()):
+        raise RuntimeError("stitch_tiles_aug: coords must be a contiguous device int32 (B, 6) tensor")
+    b, c3, ho, wo = out.shape
+    _, h, w = out_rad.shape
+    assert c3 == 3 and coords.shape[0] == b and out_rad.shape[0] == 3 and out_rad.is_contiguous() and out_rad.dtype == torch.float32
+    check(lib().wcmc_stitch_tiles_aug(_ptr(out), *out.stride(), ho, wo, patch, ctypes.c_void_p(coords.data_ptr()), b, t, h, w,
+                                      int(bool(accumulate)), _ptr(out_rad), _stream()), "stitch_tiles_aug")
+    return out_rad
+
+
+def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=True, transform=0):
     """The inference batch of the KPCN base model -- ``assemble_kpcn_patches`` without ``gt`` and without the ``target_*`` entries --
     for tiles of ``patch`` pixels at ``origins`` ((B, 2) int32 device tensor of (row, column) in frame coordinates, from ``-pad``
     upward) of the frame extended by ``pad`` pixels by mirror reflection with the edge repeated (``wcmc_assemble_kpcn_tiles``; bit
     for bit the batch of the ``np.pad(raw, pad, 'symmetric')`` frame at ``origins + pad``, which is never built).  The origins are
     data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the table once
-    (checking a device tensor here synchronises)."""
+    (checking a device tensor here synchronises).
+
+    ``transform``: a dihedral code 1..7 assembles the tiles of the frame as if the RAW frame had been transformed by ``T_t`` before
+    preprocessing (``wcmc_assemble_kpcn_tiles_aug``): ``origins`` are then in the transformed frame's
+    coordinates and are checked against its sizes (W x H for odd codes).  0 or None takes the plain call path."""
     _need_cuda(kpcn)
     _need_origins("assemble_kpcn_tiles", origins)
     h, w = kpcn.shape[:2]
     assert kpcn.shape == (h, w, 44) and kpcn.is_contiguous()
+    t = _frame_transform("assemble_kpcn_tiles", transform)
     if check_origins:
-        check_tile_origins(origins, h, w, patch, pad)
+        check_tile_origins(origins, *((w, h) if t & 1 else (h, w)), patch, pad)
     b, s = origins.shape[0], 0
     if llpm is not None:
         _need_cuda(llpm)
@@ -477,6 +528,13 @@ def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=Tr
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
     out = _aligned_views(shapes, kpcn.device)
+    if t:
+        check(lib().wcmc_assemble_kpcn_tiles_aug(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t,
+                                                 _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
+                                                 _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
+                                                 _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _stream()),
+              "assemble_kpcn_tiles_aug")
+        return out
     check(lib().wcmc_assemble_kpcn_tiles(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad,
                                          _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
                                          _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
@@ -513,14 +571,18 @@ def _finish(symbol, who, out_rad, src, llpm, preview):
 
 
 # ---------------------------------------------------------------------------------- ... with a sample-based model (csrc/sbmc_data.hip)
-def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_g_buf=True, use_sbmc_buf=True, check_origins=True):
+def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_g_buf=True, use_sbmc_buf=True, check_origins=True,
+                          transform=0):
     """The inference batch of the SBMC / LBMC interfaces -- ``assemble_sample_patches`` without ``gt`` and without ``target_image`` --
     for tiles of ``patch`` pixels at ``origins`` ((B, 2) int32 device tensor of (row, column) in frame coordinates, from ``-pad``
     upward) of the frame extended by ``pad`` pixels by mirror reflection with the edge repeated (``wcmc_assemble_sample_tiles``; bit
     for bit the ``radiance`` / ``features`` / ``paths`` of the ``np.pad(raw, pad, 'symmetric')`` frame at ``origins + pad``, which is
     never built).  ``sbmc_p`` may be None without ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  The
     origins are data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the
-    table once (checking a device tensor here synchronises)."""
+    table once (checking a device tensor here synchronises).  ``transform``: as ``assemble_kpcn_tiles``'s -- a code 1..7 reads the
+    frame through ``T_t`` (``wcmc_assemble_sample_tiles_aug``), the origins being those of the transformed frame; every channel is a
+    copy."""
+    t = _frame_transform("assemble_sample_tiles", transform)
     _need_cuda(sbmc_s)
     _need_origins("assemble_sample_tiles", origins)
     if sbmc_s.dim() != 4 or sbmc_s.shape[3] != 27 or sbmc_s.shape[2] < 1 or not sbmc_s.is_contiguous():
@@ -530,13 +592,20 @@ def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_
     if use_sbmc_buf and sbmc_p is None:
         raise ValueError("assemble_sample_tiles: use_sbmc_buf needs sbmc_p")
     if check_origins:
-        check_tile_origins(origins, h, w, patch, pad, who="assemble_sample_tiles")
+        check_tile_origins(origins, *((w, h) if t & 1 else (h, w)), patch, pad, who="assemble_sample_tiles")
     b = origins.shape[0]
     f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
     shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
     if llpm is not None:
         shapes["paths"] = (b, s, 36, patch, patch)
     out = _aligned_views(shapes, sbmc_s.device)
+    if t:
+        check(lib().wcmc_assemble_sample_tiles_aug(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
+                                                   ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t,
+                                                   int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]),
+                                                   _ptr(out["features"]), _ptr(out.get("paths")), _stream()),
+              "assemble_sample_tiles_aug")
+        return out
     check(lib().wcmc_assemble_sample_tiles(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
                                            ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, int(bool(use_g_buf)),
                                            int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),

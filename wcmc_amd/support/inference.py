@@ -149,8 +149,15 @@ def frame_tiles(h, w, patch=128, pad=32):
     return [(i0, j0, i1, j1, i, j) for i0, i1, i in spans(h) for j0, j1, j in spans(w)]
 
 
+def frame_transform_shape(h, w, t):
+    """The sizes of ``T_t`` of an h x w frame: (h, w) for the even dihedral codes, (w, h) for the odd ones."""
+    if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 7:
+        raise ValueError("frame_transform_shape: the transform code %r lies outside 0..7" % (t,))
+    return (w, h) if t & 1 else (h, w)
+
+
 def denoise_frame(interface, kpcn, llpm, use_llpm_buf=True, batch_size=8, want_pbuffers=False, patch_size=128, pad_size=32,
-                  preview=False, times=None):
+                  preview=False, times=None, ensemble=(0,)):
     """Denoise one frame of any size from its device buffers ``kpcn`` (H, W, 44) and ``llpm`` (H, W, S, 37), with no ground truth:
     per batch of ``frame_tiles`` one ``ops.assemble_kpcn_tiles`` launch, ``interface.denoise_batch`` and one ``ops.stitch_tiles``
     launch; then ``ops.finish_frame``.  ``llpm`` is always needed (``has_hit``); it feeds the network with ``use_llpm_buf``.
@@ -158,28 +165,45 @@ def denoise_frame(interface, kpcn, llpm, use_llpm_buf=True, batch_size=8, want_p
     Returns ``(out, ipt, has_hit)`` -- the denoised frame (H, W, 3) with the noisy input wherever no surface was hit, the noisy
     input (H, W, 3) and the mask (H, W) -- then the stitched P-buffers ((S, C, H, W), a dict of them, or None) when
     ``want_pbuffers``, then the two uint8 previews (of ``out`` and of ``ipt``) when ``preview``.  ``times``: a dict that receives the
-    seconds of 'network' (tiles, network, stitching) and 'finish', at the price of two device synchronisations, and 'tiles'."""
+    seconds of 'network' (tiles, network, stitching) and 'finish', at the price of two device synchronisations, and 'tiles' (with an
+    ensemble of more than one code: the tiles of all passes, and 'codes', the sorted set).
+
+    ``ensemble``: the dihedral self-ensemble, a set of distinct codes 0..7 that contains 0.  The frame is
+    denoised once per code, as if the raw frame had been transformed by ``T_t`` before preprocessing (its own tile table; the 26
+    differences retaken along the turned axes), every result is turned back, and the fp32 sum in code order is divided by the number
+    of codes.  The P-buffers, ``ipt`` and ``has_hit`` are those of the identity pass; ``(0,)`` is bit for bit the plain frame."""
     from .. import ops
     return _denoise_tiles(
         "denoise_frame", interface, kpcn,
-        lambda origins: ops.assemble_kpcn_tiles(kpcn, llpm if use_llpm_buf else None, origins, patch_size, pad_size,
-                                                check_origins=False),
+        lambda origins, t=0: ops.assemble_kpcn_tiles(kpcn, llpm if use_llpm_buf else None, origins, patch_size, pad_size,
+                                                     check_origins=False, transform=t),
         lambda out_rad: ops.finish_frame(out_rad, kpcn, llpm, preview=preview),
-        batch_size, want_pbuffers, patch_size, pad_size, preview, times)
+        batch_size, want_pbuffers, patch_size, pad_size, preview, times, ensemble=ensemble)
 
 
 def _denoise_tiles(who, interface, frame, assemble, finish, batch_size, want_pbuffers, patch_size, pad_size, preview, times,
-                   check_output=False):
+                   check_output=False, ensemble=(0,)):
     """THE frame driver behind ``denoise_frame`` and ``denoise_sample_frame`` (``who``): the tile table of ``frame``, a device buffer (H, W, ...)
     of the family, and its host checks, ``_stitch_batches`` over ``assemble(origins)`` -- the family's batch for a device (B, 2) slice of the tile
     origins -- and ``interface.denoise_batch``, then ``finish(out_rad)``, the family's closing op, and the return tuple.
-    ``check_output``: ``check_output_size`` on the first batch's output.  A third model family supplies the two closures."""
+    ``check_output``: ``check_output_size`` on the first batch's output.  A third model family supplies the two closures.
+    ``ensemble``: after the identity pass, one pass per further code t over the tile table of the transformed frame --
+    ``assemble(origins, t)``, ``interface.denoise_batch``, ``ops.stitch_tiles_aug`` adding into the same ``out_rad`` -- then one
+    division by the number of codes (``denoise_frame``)."""
     import time
     from .. import ops
     (h, w), device = frame.shape[:2], frame.device
+    codes = ops.check_frame_transforms(ensemble)
     coords = frame_tiles(h, w, patch_size, pad_size)
     ops.check_tile_coords(coords, h, w, patch_size)
     ops.check_tile_origins([c[4:6] for c in coords], h, w, patch_size, pad_size, who=who)
+    tables = {(h, w): coords}                                    # one table per shape of the transformed frame: at most two
+    for t in codes[1:]:
+        ht, wt = frame_transform_shape(h, w, t)
+        if (ht, wt) not in tables:
+            tables[(ht, wt)] = frame_tiles(ht, wt, patch_size, pad_size)
+            ops.check_tile_coords(tables[(ht, wt)], ht, wt, patch_size)
+            ops.check_tile_origins([c[4:6] for c in tables[(ht, wt)]], ht, wt, patch_size, pad_size, who=who)
     interface.to_eval_mode()
     if times is not None:
         torch.cuda.synchronize(device)
@@ -190,13 +214,26 @@ def _denoise_tiles(who, interface, frame, assemble, finish, batch_size, want_pbu
         batches = ((assemble(origins_dev[k:k + batch_size]), coords_dev[k:k + batch_size]) for k in range(0, len(coords), batch_size))
         first = (lambda out: check_output_size(out.shape[2], out.shape[3], patch_size, pad_size)) if check_output else None
         out_rad, out_path = _stitch_batches(batches, interface.denoise_batch, h, w, want_pbuffers, patch_size, first)
+        tiles = len(coords)
+        for t in codes[1:]:
+            table = tables[frame_transform_shape(h, w, t)]
+            table_dev = coords_dev if table is coords else torch.tensor(table, dtype=torch.int32, device=device)
+            org_dev = table_dev[:, 4:6].contiguous()
+            for k in range(0, len(table), batch_size):
+                out, _ = interface.denoise_batch(assemble(org_dev[k:k + batch_size], t))
+                ops.stitch_tiles_aug(out, table_dev[k:k + batch_size], out_rad, t, True, patch_size)
+            tiles += len(table)
+        if len(codes) > 1:
+            out_rad = out_rad / torch.full((), len(codes), dtype=out_rad.dtype, device=device)      # one fp32 division
         if times is not None:
             torch.cuda.synchronize(device)
             t1 = time.perf_counter()
         res = finish(out_rad)
         if times is not None:
             torch.cuda.synchronize(device)
-            times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=len(coords))
+            times.update(network=t1 - t0, finish=time.perf_counter() - t1, tiles=tiles)
+            if len(codes) > 1:                                   # (an un-ensembled frame reports what it always did)
+                times.update(codes=codes)
     return res[:3] + ((out_path,) if want_pbuffers else ()) + (tuple(res[3:]) if preview else ())
 
 
@@ -211,18 +248,19 @@ def check_output_size(ho, wo, patch_size, pad_size):
 
 
 def denoise_sample_frame(interface, sbmc_s, sbmc_p, llpm, use_llpm_buf=True, use_g_buf=True, use_sbmc_buf=True, batch_size=8,
-                         want_pbuffers=False, patch_size=128, pad_size=32, preview=False, times=None):
+                         want_pbuffers=False, patch_size=128, pad_size=32, preview=False, times=None, ensemble=(0,)):
     """``denoise_frame`` for the sample-based interfaces (``SBMCInterface`` / ``LBMCInterface`` around the caller's denoiser), from
     the device buffers ``sbmc_s`` (H, W, S, 27), ``sbmc_p`` (H, W, S, 66; None without ``use_sbmc_buf``) and ``llpm`` (H, W, S, 37):
     per batch of ``frame_tiles`` one ``ops.assemble_sample_tiles`` launch, ``interface.denoise_batch`` and one ``ops.stitch_tiles``
     launch; then ``ops.finish_sample_frame``.  ``llpm`` is always needed (``has_hit``); it feeds the network with ``use_llpm_buf``.
     The denoiser's receptive field is the caller's: an output so small that replicated pixels would reach an owned window is a
     ``ValueError`` after the first batch (``check_output_size``).  Returns what ``denoise_frame`` returns; the P-buffer is one
-    (S, C, H, W) tensor."""
+    (S, C, H, W) tensor.  ``ensemble``: as ``denoise_frame``'s; every channel of these buffers is a copy under a transform."""
     from .. import ops
     return _denoise_tiles(
         "denoise_sample_frame", interface, sbmc_s,
-        lambda origins: ops.assemble_sample_tiles(sbmc_s, sbmc_p if use_sbmc_buf else None, llpm if use_llpm_buf else None, origins,
-                                                  patch_size, pad_size, use_g_buf, use_sbmc_buf, check_origins=False),
+        lambda origins, t=0: ops.assemble_sample_tiles(sbmc_s, sbmc_p if use_sbmc_buf else None, llpm if use_llpm_buf else None,
+                                                       origins, patch_size, pad_size, use_g_buf, use_sbmc_buf, check_origins=False,
+                                                       transform=t),
         lambda out_rad: ops.finish_sample_frame(out_rad, sbmc_s, llpm, preview=preview),
-        batch_size, want_pbuffers, patch_size, pad_size, preview, times, check_output=True)
+        batch_size, want_pbuffers, patch_size, pad_size, preview, times, check_output=True, ensemble=ensemble)
