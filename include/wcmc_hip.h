@@ -852,6 +852,21 @@ int wcmc_assemble_sample_tiles_aug(const float* sbmc_s, const float* sbmc_p, con
 int wcmc_stitch_tiles_aug(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,
                           const int* coords, int B, int t, int H, int W, int accumulate, float* out_rad, void* stream);
 
+/* The feathered stitch: radiance blended across the seams of the owned windows.
+ * stitch_tiles_blend: for every tile b of the batch, in table order, and every pixel (y, x) of [i_start - F, i_end + F) x
+ *   [j_start - F, j_end + F) clipped to the frame transformed by code t (t = 0: the frame itself), acc[:, sy, sx] += w * v and
+ *   wsum[sy, sx] += w; v is read as stitch_tiles_aug reads it, (sy, sx) is the pixel's source, and w = u_rows(y) * u_cols(x) with
+ *   u(x) = L(x) * R(x), L = 1 where i_start == 0, else clamp((x - i_start + F + 0.5) / (2F), 0, 1), R = 1 where i_end is the axis'
+ *   length, else clamp((i_end + F - x - 0.5) / (2F), 0, 1); F = 0: w = 1 on the owned window.  acc (3, H, W) and wsum (H, W) are
+ *   contiguous fp32 in SOURCE orientation and zero before the first batch of a pass.  One thread owns a destination pixel and adds the
+ *   batch's tiles in order: no atomics, and the sums do not depend on how the table is cut into batches.  pad: the pad of the table,
+ *   or negative where the caller vouches for it; with a pad, 2F <= P - 2 pad (at most three tiles meet on an axis) and
+ *   F <= pad - max((P - ho + 1) / 2, (P - wo + 1) / 2) (no replicated pixel carries weight) are required.
+ * blend_finish: out_rad (3, H, W) = acc / wsum (accumulate = 0) or out_rad + acc / wsum (accumulate = 1). */
+int wcmc_stitch_tiles_blend(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P, int pad,
+                            const int* coords, int B, int t, int H, int W, int F, float* acc, float* wsum, void* stream);
+int wcmc_blend_finish(const float* acc, const float* wsum, int H, int W, int accumulate, float* out_rad, void* stream);
+
 /* ---------------------------------------------------------------- filtering a frame by its P-buffer (csrc/pbuffer_filter.hip)
  * Non-local means whose patch distance is taken between the per-pixel statistics of the path embedding (Ray Histogram Fusion with
  * the learned manifold in place of the colour histograms).  The build's own specification: DESIGN.md section 19.

@@ -147,6 +147,8 @@ SIGNATURES = {
     "wcmc_assemble_kpcn_tiles_aug": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P]),
     "wcmc_assemble_sample_tiles_aug": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
     "wcmc_stitch_tiles_aug": (I, [P, L, L, L, L, I, I, I, P, I, I, I, I, I, P, P]),
+    "wcmc_stitch_tiles_blend": (I, [P, L, L, L, L, I, I, I, I, P, I, I, I, I, I, P, P, P]),
+    "wcmc_blend_finish": (I, [P, P, I, I, I, P, P]),
     "wcmc_pbuffer_filter_workspace_bytes": (Z, [I, I, I, I]),
     "wcmc_pbuffer_filter": (I, [P, L, L, L, P, L, L, L, L, P, I, P, P, P, Z, I, I, I, I, I, I, I, F, F, I, P]),
 }

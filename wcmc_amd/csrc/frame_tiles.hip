@@ -10,6 +10,9 @@
 // The dihedral self-ensemble adds the way through a whole-frame transform and back:
 //   wcmc_assemble_kpcn_tiles_aug  the same batch of the frame as if the RAW frame had been flipped / turned before preprocessing.
 //   wcmc_stitch_tiles_aug         pastes or adds the owned windows of the transformed frame's tiles into the frame in source orientation.
+// Feathered seams:
+//   wcmc_stitch_tiles_blend       adds w * v and w of one batch of tiles, each on its owned window widened by F pixels, under a code t.
+//   wcmc_blend_finish             out = acc / wsum, or out += acc / wsum: a pass normalised by its own weight sum.
 #include "data_step.h"
 
 namespace wcmc {
@@ -224,9 +227,135 @@ __global__ __launch_bounds__(256) void ft_stitch_aug_kernel(StitchAugArgs a) {
   }
 }
 
+// The feathered stitch: every tile of the batch adds w * v and w on [i_start - F, i_end + F) x [j_start - F,
+// j_end + F) of the (transformed) frame, clipped to it.  One thread owns a destination pixel for the whole launch and walks the
+// batch's tiles in table order, so the fp32 sums are those of the table order whatever the batches are, with no atomic; launches
+// follow one another on one stream.  Every thread first takes the bounding box of the batch's ranges (B uniform reads of the table)
+// and the grid strides over that box alone: a batch is a few tiles of a frame of many.
+struct StitchBlendArgs {
+  const float* rad; int64_t rsb, rsc, rsh, rsw;     // (B, 3, ho, wo) network output
+  const int* coords;                                // (B, 6) rows of the transformed frame's table
+  float *acc, *wsum;                                // (3, H, W), (H, W): source orientation
+  int ho, wo, P, B, H, W, t, F;
+};
+
+// a table row that ie_stitch_kernel would skip is skipped here too
+__device__ __forceinline__ bool ft_row_ok(const int* cd, int Ht, int Wt, int P) {
+  const int i0 = cd[0], j0 = cd[1], i1 = cd[2], j1 = cd[3], ib = cd[4], jb = cd[5];
+  return !(i0 < 0 || j0 < 0 || i1 > Ht || j1 > Wt || i0 >= i1 || j0 >= j1 || i0 < ib || j0 < jb || i1 > ib + P || j1 > jb + P);
+}
+
+// u(x) = L(x) * R(x) of section 22 along an axis of length n for the owned interval [a, b), inside [a - F, b + F) and F > 0.  The
+// numerators are odd integers over 4F: exact in fp64, so the 2-D weight is rounded once, on its way to fp32.
+__device__ __forceinline__ double ft_feather(int x, int a, int b, int n, int F) {
+  const double den = 4.0 * F;
+  const double l = a == 0 ? 1.0 : fmin(fmax((double)(2 * (x - a + F) + 1) / den, 0.0), 1.0);
+  const double r = b == n ? 1.0 : fmin(fmax((double)(2 * (b + F - x) - 1) / den, 0.0), 1.0);
+  return l * r;
+}
+
+__global__ __launch_bounds__(256) void ft_stitch_blend_kernel(StitchBlendArgs a) {
+  const int Ht = a.t & 1 ? a.W : a.H, Wt = a.t & 1 ? a.H : a.W;
+  int y0 = Ht, y1 = 0, x0 = Wt, x1 = 0;
+  for (int b = 0; b < a.B; ++b) {
+    const int* cd = a.coords + 6 * b;
+    if (!ft_row_ok(cd, Ht, Wt, a.P)) continue;
+    y0 = min(y0, max(cd[0] - a.F, 0)); y1 = max(y1, min(cd[2] + a.F, Ht));
+    x0 = min(x0, max(cd[1] - a.F, 0)); x1 = max(x1, min(cd[3] + a.F, Wt));
+  }
+  if (y0 >= y1 || x0 >= x1) return;
+  const int bw = x1 - x0;
+  const int64_t box = (int64_t)(y1 - y0) * bw, hw = (int64_t)a.H * a.W;
+  const int top = (a.P - a.ho) / 2, left = (a.P - a.wo) / 2;      // the 'replicate' padding of ie_stitch_kernel
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < box; e += (int64_t)gridDim.x * blockDim.x) {
+    const int y = y0 + (int)(e / bw), x = x0 + (int)(e % bw);     // pixel of the transformed frame
+    float s[3] = {0.f, 0.f, 0.f}, sw = 0.f;
+    bool any = false;
+    const FramePos p = frame_map(a.t, y, x, a.H, a.W);
+    const int64_t dst = (int64_t)p.sy * a.W + p.sx;
+    for (int b = 0; b < a.B; ++b) {
+      const int* cd = a.coords + 6 * b;
+      if (!ft_row_ok(cd, Ht, Wt, a.P)) continue;
+      const int i0 = cd[0], j0 = cd[1], i1 = cd[2], j1 = cd[3], ib = cd[4], jb = cd[5];
+      if (y < i0 - a.F || y >= i1 + a.F || x < j0 - a.F || x >= j1 + a.F) continue;
+      const float w = a.F == 0 ? 1.f : (float)(ft_feather(y, i0, i1, Ht, a.F) * ft_feather(x, j0, j1, Wt, a.F));
+      const int sy = min(max(y - ib - top, 0), a.ho - 1), sx = min(max(x - jb - left, 0), a.wo - 1);
+      const float* v = a.rad + b * a.rsb + sy * a.rsh + sx * a.rsw;
+      if (!any) {                                                 // the sums of earlier launches: read once, where a tile contributes
+        any = true;
+        sw = a.wsum[dst];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) s[ch] = a.acc[ch * hw + dst];
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) s[ch] = s[ch] + w * v[ch * a.rsc];
+      sw = sw + w;
+    }
+    if (any) {
+      a.wsum[dst] = sw;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) a.acc[ch * hw + dst] = s[ch];
+    }
+  }
+}
+
+// out = acc / wsum, or out + acc / wsum: the pass of one transform code, normalised by its own weight sum
+template <bool ACC>
+__global__ __launch_bounds__(256) void ft_blend_finish_kernel(const float* __restrict__ acc, const float* __restrict__ wsum, int64_t npix,
+                                                              float* __restrict__ out) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const float w = wsum[p];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float q = acc[ch * npix + p] / w;
+      out[ch * npix + p] = ACC ? out[ch * npix + p] + q : q;
+    }
+  }
+}
+
 }  // namespace wcmc
 
 using namespace wcmc;
+
+extern "C" int wcmc_stitch_tiles_blend(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,
+                                       int pad, const int* coords, int B, int t, int H, int W, int F, float* acc, float* wsum,
+                                       void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: the transform code must lie in 0..7 (got %d)", t);
+  WCMC_REQUIRE(rad && coords && acc && wsum, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: null pointer");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: B, H, W, P must be positive");
+  WCMC_REQUIRE((ho == P && wo == P) || (ho > 0 && wo > 0 && ho < P && wo < P), WCMC_ERR_BAD_ARG,
+               "stitch_tiles_blend: the %d x %d network output must be P x P or smaller in both dimensions (P = %d)", ho, wo, P);
+  WCMC_REQUIRE(F >= 0, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: the feather half-width must not be negative (got %d)", F);
+  WCMC_REQUIRE(F <= P, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: a feather half-width of %d is wider than the %d-pixel tile", F, P);
+  if (pad >= 0) {                                                 // (a negative pad: the caller vouches for the table)
+    WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+    WCMC_REQUIRE(2 * F <= P - 2 * pad, WCMC_ERR_BAD_ARG,
+                 "stitch_tiles_blend: the two ramps of 2 * %d pixels are longer than the %d-pixel interior of a tile (P %d - 2 * pad %d)",
+                 F, P - 2 * pad, P, pad);
+    const int inset = (P - ho + 1) / 2 > (P - wo + 1) / 2 ? (P - ho + 1) / 2 : (P - wo + 1) / 2;
+    WCMC_REQUIRE(F <= pad - inset, WCMC_ERR_BAD_ARG,
+                 "stitch_tiles_blend: a feather of %d pixels beyond a pad of %d reaches the %d replicated pixels of the %d x %d output",
+                 F, pad, inset, ho, wo);
+  }
+  WCMC_REQUIRE(B <= 65535, WCMC_ERR_BAD_ARG, "stitch_tiles_blend: at most 65535 tiles per launch");
+  StitchBlendArgs a{rad, rsb, rsc, rsh, rsw, coords, acc, wsum, ho, wo, P, B, H, W, t, F};
+  int64_t work = (int64_t)B * P * P;                              // every range lies inside its tile: the box is seldom larger
+  if (work > (int64_t)H * W) work = (int64_t)H * W;
+  hipLaunchKernelGGL(ft_stitch_blend_kernel, dim3(pp_grid(work)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("stitch_tiles_blend");
+}
+
+extern "C" int wcmc_blend_finish(const float* acc, const float* wsum, int H, int W, int accumulate, float* out_rad, void* stream) {
+  WCMC_REQUIRE(acc && wsum && out_rad, WCMC_ERR_BAD_ARG, "blend_finish: null pointer");
+  WCMC_REQUIRE(H > 0 && W > 0, WCMC_ERR_BAD_ARG, "blend_finish: H and W must be positive (got %d, %d)", H, W);
+  WCMC_REQUIRE(accumulate == 0 || accumulate == 1, WCMC_ERR_BAD_ARG, "blend_finish: accumulate must be 0 or 1 (got %d)", accumulate);
+  const int64_t npix = (int64_t)H * W;
+  if (accumulate)
+    hipLaunchKernelGGL(ft_blend_finish_kernel<true>, dim3(pp_grid(npix)), dim3(256), 0, (hipStream_t)stream, acc, wsum, npix, out_rad);
+  else
+    hipLaunchKernelGGL(ft_blend_finish_kernel<false>, dim3(pp_grid(npix)), dim3(256), 0, (hipStream_t)stream, acc, wsum, npix, out_rad);
+  return check_launch("blend_finish");
+}
 
 extern "C" int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S,
                                         float* out, float* ipt, float* has_hit, unsigned char* preview_out,

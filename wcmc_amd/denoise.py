@@ -1,7 +1,7 @@
 """Denoise raw renders of any size with a trained KPCN, SBMC or LBMC model: no ground truth, no offline files, every pixel.
 
     python -m wcmc_amd.denoise --input A.npy [B.npy ...] --output_dir OUT --save WEIGHTS_DIR --model_name KPCN_manifold \\
-        [--spp N] [--tile_batch B] [--band_rows N] [--png] [--save_pbuffer] [--rhf] [--self_ensemble [CODE ...]] \\
+        [--spp N] [--tile_batch B] [--tile P] [--tile_pad N] [--blend F] [--band_rows N] [--png] [--save_pbuffer] [--rhf] [--self_ensemble [CODE ...]] \\
         [--use_llpm_buf --manif_learn --manif_loss FMSE ...]
     python -m wcmc_amd.denoise ... --model_name SBMC_manifold --denoiser my_pkg.models:make_multisteps [--use_sbmc_buf] [--tile_pad N]
 
@@ -21,8 +21,13 @@ and averages them; the P-buffer stays the un-ensembled on
 A model whose name holds ``SBMC`` / ``LBMC`` is a ``train_sbmc`` / ``train_lbmc`` checkpoint around the caller's base denoiser
 (``--denoiser package.module:factory``, required; ``--disentangle``, ``--use_sbmc_buf``, ``--lr_dncnn`` as those launchers define them).
 Its frames are streamed as ``sbmc_s`` / ``sbmc_p`` / ``llpm`` and run through ``support.inference.denoise_sample_frame``; the P-buffer
-is one tensor.  ``--tile_pad N`` (default 32) is the overlap of the 128-pixel tiles: the denoiser's receptive field is the caller's,
-and an output that leaves fewer real pixels than the pad is refused.  For the KPCN models the pad is 32.
+is one tensor.  ``--tile_pad N`` (default 32) is the overlap of the tiles: the denoiser's receptive field is the caller's,
+and an output that leaves fewer real pixels than the pad is refused.
+
+``--tile P`` (a multiple of 64 in 128..512, default 128) is the tile side, ``--tile_pad N`` the overlap (KPCN models: at least 32, and
+``P - 2 N >= 64``), ``--blend F`` (default 0) the half-width of a feather that blends the radiance of neighbouring tiles over the
+``2 F`` pixels around every seam (KPCN: ``F <= N - 28``; sample-based: ``N`` minus the denoiser's inset; ``2 F <= P - 2 N``).  DESIGN.md
+section 22; 128 / 32 / 0 is section 15's path bit for bit.
 """
 import os
 import struct
@@ -34,7 +39,7 @@ import torch
 
 from . import ops, rhf, train_kpcn
 from .support.datasets import MAX_CONTINUATIONS, dncnn_in_size
-from .support.inference import denoise_frame, denoise_sample_frame, frame_tiles
+from .support.inference import (KPCN_INSET, check_blend, check_tile_fits, denoise_frame, denoise_sample_frame, frame_tiles)
 from .support.staging import FrameStreamer
 
 PATCH_SIZE, PAD_SIZE = 128, 32
@@ -67,18 +72,70 @@ def write_png(fn, img):
 
 
 # ------------------------------------------------------------------------------------------------- input
-def tile_batch_size(spp, tile_batch=None):
-    """Tiles per network call: 8 up to 32 spp, 4 up to 64 (test_models.py:147-161); above that the caller decides."""
+def tile_batch_size(spp, tile_batch=None, tile=PATCH_SIZE):
+    """Tiles per network call: 8 up to 32 spp, 4 up to 64 (test_models.py:147-161) for the 128-pixel tile; a larger ``tile`` keeps that
+    pixel budget per call, ``max(1, B128 * 128^2 // tile^2)``.  Above 64 spp the caller decides."""
     if tile_batch is not None:
         if tile_batch < 1:
             raise ValueError("--tile_batch should be at least 1, got %d" % tile_batch)
         return tile_batch
     if spp <= 32:
-        return 8
+        return max(1, 8 * PATCH_SIZE * PATCH_SIZE // (tile * tile))
     if spp <= 64:
-        return 4
+        return max(1, 4 * PATCH_SIZE * PATCH_SIZE // (tile * tile))
     raise ValueError("no default tile batch size above 64 samples per pixel (got %d): give --tile_batch after looking at the "
                      "device's memory" % spp)
+
+
+TILE_LIMITS = (
+    # (the kernel's limit as its WCMC_REQUIRE states it, the quantity for tiles of P pixels, pad, S samples, B tiles per call, the bound)
+    ("to_nhwc / from_nhwc / split_from_nchw: N * H <= 65535 rows per launch (N = B * S for the per-sample tensors)",
+     lambda P, pad, S, B: B * S * P, 65535),
+    ("final2 / embed3: B * S * H * W * 256 bytes < 0x7ff00000 (the 64-channel per-sample activations in one 2 GiB buffer view)",
+     lambda P, pad, S, B: B * S * P * P * 256, 0x7ff00000 - 1),
+    ("conv2d: every operand below 2 GiB (the 21 x 21 kernel logits, 441 channels padded to 448 fp32, of one call)",
+     lambda P, pad, S, B: B * P * P * 448 * 4, 0x7ff00000 - 1),
+    # (kernel_splat's h * w < 2^30 and N <= 65535 and the stitches' B <= 65535 lie behind the first row for every tile of 128..512)
+)
+
+
+def check_tile_limits(tile, pad, spp, tile_batch, per_sample=True):
+    """The hard limits that the kernels of the inference forward state in their argument checks, collected: a ``(tile, pad, spp,
+    tile_batch)`` that crosses one is refused here, before anything is launched, with the flags to turn and the limit.  No limit is
+    lifted; a combination that passes here and is refused by a kernel all the same is a limit missing from ``TILE_LIMITS``.
+    ``per_sample``: the model holds per-sample tensors (``--use_llpm_buf``, SBMC / LBMC); without them the limits are those of S = 1.
+    One tile of a per-sample model reaches final2's 2 GiB view at 64 spp and 384 pixels and at 32 spp and 512: such frames take a smaller tile."""
+    for what, quantity, bound in TILE_LIMITS:
+        q = quantity(tile, pad, spp if per_sample else 1, tile_batch)
+        if q > bound:
+            raise ValueError("--tile %d with --tile_batch %d at %d samples per pixel crosses a kernel's limit (%d > %d): %s.  Give a "
+                             "smaller --tile or --tile_batch" % (tile, tile_batch, spp, q, bound, what))
+    return tile_batch
+
+
+def _per_sample(args):
+    return bool(args.use_llpm_buf) or sample_launcher(args.model_name) is not None
+
+
+def check_tile_flags(args):
+    """``--tile``, ``--tile_pad`` and ``--blend`` against one another, before any file is looked for.  KPCN
+    models: ``32 <= pad``, ``tile - 2 * pad >= 64`` and ``blend <= pad - 28``; the sample-based models' inset is their denoiser's and
+    is checked on the first batch.  Returns (tile, pad, blend)."""
+    tile, pad, blend = getattr(args, 'tile', PATCH_SIZE), getattr(args, 'tile_pad', PAD_SIZE), getattr(args, 'blend', 0)
+    if tile % 64 or not 128 <= tile <= 512:
+        raise ValueError("--tile %d: the tile side should be a multiple of 64 in 128..512" % tile)
+    sample = sample_launcher(args.model_name) is not None
+    if sample:
+        frame_tiles(2 * tile, 2 * tile, tile, pad)                                      # (a pad without an interior)
+    else:
+        if pad < PAD_SIZE:
+            raise ValueError("--tile_pad %d: the KPCN models need a pad of at least %d, the one their receptive field was checked "
+                             "against (DESIGN.md section 15)" % (pad, PAD_SIZE))
+        if tile - 2 * pad < 64:
+            raise ValueError("--tile_pad %d with --tile %d leaves a tile an interior of %d pixels; the KPCN models are run with at "
+                             "least 64" % (pad, tile, tile - 2 * pad))
+    check_blend("denoise", blend, tile, pad, None if sample else KPCN_INSET)
+    return tile, pad, blend
 
 
 def _open_raw(fn):
@@ -172,17 +229,19 @@ def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, prepro
     t1 = time.perf_counter()
     llpm = bufs[-1]
     h, w, spp = llpm.shape[:3]
-    batch_size = tile_batch_size(spp, args.tile_batch)
+    tile, pad, blend = getattr(args, 'tile', PATCH_SIZE), getattr(args, 'tile_pad', PAD_SIZE), getattr(args, 'blend', 0)
+    batch_size = check_tile_limits(tile, pad, spp, tile_batch_size(spp, args.tile_batch, tile), _per_sample(args))
     times = {}
     want_rhf = getattr(args, 'rhf', False)
     want_p = args.save_pbuffer or want_rhf
     if sample_launcher(args.model_name) is not None:
         res = denoise_sample_frame(interface, bufs[0], bufs[1], llpm, args.use_llpm_buf, args.use_g_buf, args.use_sbmc_buf,
-                                   batch_size, want_pbuffers=want_p, patch_size=PATCH_SIZE, pad_size=args.tile_pad,
-                                   preview=args.png, times=times, ensemble=ensemble_codes(args))
+                                   batch_size, want_pbuffers=want_p, patch_size=tile, pad_size=pad,
+                                   preview=args.png, times=times, ensemble=ensemble_codes(args), blend=blend)
     else:
         res = denoise_frame(interface, bufs[0], llpm, args.use_llpm_buf, batch_size, want_pbuffers=want_p,
-                            patch_size=PATCH_SIZE, pad_size=PAD_SIZE, preview=args.png, times=times, ensemble=ensemble_codes(args))
+                            patch_size=tile, pad_size=pad, preview=args.png, times=times, ensemble=ensemble_codes(args),
+                            blend=blend)
     out, out_path = res[0], (res[3] if want_p else None)
     os.makedirs(output_dir, exist_ok=True)
     img = out.cpu().numpy()
@@ -202,9 +261,11 @@ def _denoise_buffers(interface, stem, bufs, output_dir, args, upload=0.0, prepro
             raise ValueError("--rhf: the model computes no P-buffer (it needs --use_llpm_buf)")
         f_out, f_wsum = rhf.rhf_filter(res[1], out_path, res[2], **rhf_arguments(args))
         rhf.write_outputs(output_dir, stem, f_out, f_wsum, args.rhf_radius, png=args.png)
-    times.update(upload=upload, preprocess=preprocess, write=time.perf_counter() - t1 - times['network'] - times['finish'])
-    print("%s: %d x %d, %d spp, tiles of %d per call: upload %.3f s, preprocess %.3f s, network %.3f s, finish %.3f s"
-          % (stem, h, w, spp, batch_size, times['upload'], times['preprocess'], times['network'], times['finish']))
+    times.update(upload=upload, preprocess=preprocess, write=time.perf_counter() - t1 - times['network'] - times['finish'],
+                 tile=tile, tile_pad=pad, blend=blend)
+    print("%s: %d x %d, %d spp, %d tiles of %d pixels, %d per call: upload %.3f s, preprocess %.3f s, network %.3f s, finish %.3f s"
+          % (stem, h, w, spp, times['tiles'], tile, batch_size, times['upload'], times['preprocess'], times['network'],
+             times['finish']))
     return times
 
 
@@ -295,9 +356,16 @@ def build_parser():
                         'time grows with the number of codes; meant for models trained with --augment')
     rhf.add_filter_arguments(p, prefix='rhf_')
     add_sample_arguments(p)
+    p.add_argument('--tile', type=int, default=PATCH_SIZE, metavar='P',
+                   help='side of the tiles the network is run on: a multiple of 64 in 128..512 (default 128).  A larger tile throws '
+                        'less of every convolution away ((P / (P - 2 N))^2 of the work per pixel) and needs more memory per call')
     p.add_argument('--tile_pad', type=int, default=PAD_SIZE, metavar='N',
-                   help='overlap of the 128-pixel tiles on each side (SBMC / LBMC: at least what the denoiser\'s receptive field '
-                        'takes off a side of a tile; KPCN models: 32)')
+                   help='overlap of the tiles on each side (SBMC / LBMC: at least what the denoiser\'s receptive field '
+                        'takes off a side of a tile; KPCN models: at least 32, and P - 2 N at least 64): context around the pixels '
+                        'a tile owns')
+    p.add_argument('--blend', type=int, default=0, metavar='F',
+                   help='feather the seams between tiles over 2 F pixels (default 0: each pixel comes from the one tile that owns '
+                        'it).  KPCN models: F <= N - 28; SBMC / LBMC: F <= N - what the denoiser takes off a side; 2 F <= P - 2 N')
     return p
 
 
@@ -337,15 +405,16 @@ def check_inputs(args):
     if sample_launcher(args.model_name) is not None:
         from .train_sbmc import load_denoiser_factory
         load_denoiser_factory(getattr(args, 'denoiser', None))        # (a DenoiserFactoryError, before any file is looked for)
-        frame_tiles(2 * PATCH_SIZE, 2 * PATCH_SIZE, PATCH_SIZE, args.tile_pad)          # (a pad without an interior)
-    elif getattr(args, 'tile_pad', PAD_SIZE) != PAD_SIZE:
-        raise ValueError("--tile_pad %d: the KPCN models are run with a pad of %d, the one their receptive field was checked "
-                         "against (DESIGN.md section 15)" % (args.tile_pad, PAD_SIZE))
+    tile, pad, _ = check_tile_flags(args)
+    codes = ensemble_codes(args)
     if getattr(args, 'band_rows', None) is not None and args.band_rows < 1:
         raise ValueError("--band_rows should be at least 1, got %d" % args.band_rows)
     for fn in args.input:
-        _, spp = read_raw(fn, args.spp)
-        tile_batch_size(spp, args.tile_batch)
+        parts, spp = read_raw(fn, args.spp)
+        batch_size = tile_batch_size(spp, args.tile_batch, tile)
+        if (tile, pad) != (PATCH_SIZE, PAD_SIZE):       # (at the default tiling a frame is refused where it always was: frame_tiles)
+            check_tile_fits("denoise: " + fn, parts[0].shape[0], parts[0].shape[1], tile, pad, codes)
+        check_tile_limits(tile, pad, spp, batch_size, _per_sample(args))
     if args.save_pbuffer and not args.use_llpm_buf:
         raise ValueError("--save_pbuffer: the model computes no P-buffer (it needs --use_llpm_buf)")
     if getattr(args, 'rhf', False):

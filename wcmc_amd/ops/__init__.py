@@ -182,4 +182,5 @@ from .data import (_need_dense, preprocess_llpm, preprocess_kpcn, assemble_kpcn_
                    importance_map, sampling_prob, sanitize_, random_permutation, random_permutation_dev, step_counter_advance,
                    permutation_key, check_tile_coords, stitch_tiles, preprocess_sbmc, check_patch_origins, sample_feature_size,
                    assemble_sample_patches, preprocess_kpcn_prefix, check_tile_origins, assemble_kpcn_tiles, finish_frame,
-                   assemble_sample_tiles, finish_sample_frame, check_patch_transforms, check_frame_transforms, stitch_tiles_aug)
+                   assemble_sample_tiles, finish_sample_frame, check_patch_transforms, check_frame_transforms, stitch_tiles_aug,
+                   stitch_tiles_blend, blend_finish)

@@ -498,6 +498,43 @@ def stitch_tiles_aug(out, coords, out_rad, transform, accumulate, patch=128):
     return out_rad
 
 
+def stitch_tiles_blend(out, coords, acc, wsum, blend, transform=0, patch=128, pad=None):
+    """The feathered stitch (``wcmc_stitch_tiles_blend``): every tile of the batch adds ``w * v`` to ``acc``
+    (3, H, W) and ``w`` to ``wsum`` (H, W), both fp32, contiguous, in SOURCE orientation and zero before the first batch of a pass, on
+    its owned window widened by ``blend`` pixels; ``w`` ramps from 0 to 1 over the ``2 * blend`` pixels around every seam.  out:
+    (B, 3, ho, wo) network output, read as ``stitch_tiles`` reads it; coords: device int32 (B, 6) rows of the table of the frame
+    transformed by code ``transform``, which passed ``check_tile_coords``.  The tiles are added in table order by the one thread that
+    owns the pixel: the sums do not depend on how the table is cut into batches.  ``pad``: the table's pad; with it the library also
+    refuses a ``blend`` above ``(patch - 2 * pad) / 2`` or one that gives weight to a replicated pixel.  No P-buffers."""
+    _need_cuda(out, acc, wsum)
+    t = _frame_transform("stitch_tiles_blend", transform)
+    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
+            and coords.is_contiguous()):
+        raise RuntimeError("stitch_tiles_blend: coords must be a contiguous device int32 (B, 6) tensor")
+    if isinstance(blend, bool) or not isinstance(blend, numbers.Integral):
+        raise ValueError("stitch_tiles_blend: the feather half-width should be an integer, got %r" % (blend,))
+    b, c3, ho, wo = out.shape
+    _, h, w = acc.shape
+    assert c3 == 3 and coords.shape[0] == b and out.dtype == torch.float32
+    assert acc.shape[0] == 3 and acc.is_contiguous() and acc.dtype == torch.float32
+    assert tuple(wsum.shape) == (h, w) and wsum.is_contiguous() and wsum.dtype == torch.float32
+    check(lib().wcmc_stitch_tiles_blend(_ptr(out), *out.stride(), ho, wo, patch, -1 if pad is None else int(pad),
+                                        ctypes.c_void_p(coords.data_ptr()), b, t, h, w, int(blend), _ptr(acc), _ptr(wsum), _stream()),
+          "stitch_tiles_blend")
+    return acc, wsum
+
+
+def blend_finish(acc, wsum, out_rad, accumulate=False):
+    """``out_rad`` (3, H, W) = ``acc / wsum`` or, with ``accumulate``, ``out_rad + acc / wsum`` (``wcmc_blend_finish``): the pass of one
+    transform code, normalised by its own weight sum.  Returns out_rad."""
+    _need_cuda(acc, wsum, out_rad)
+    _, h, w = acc.shape
+    for x, shape in ((acc, (3, h, w)), (wsum, (h, w)), (out_rad, (3, h, w))):
+        assert tuple(x.shape) == shape and x.is_contiguous() and x.dtype == torch.float32
+    check(lib().wcmc_blend_finish(_ptr(acc), _ptr(wsum), h, w, int(bool(accumulate)), _ptr(out_rad), _stream()), "blend_finish")
+    return out_rad
+
+
 def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=True, transform=0):
     """The inference batch of the KPCN base model -- ``assemble_kpcn_patches`` without ``gt`` and without the ``target_*`` entries --
     for tiles of ``patch`` pixels at ``origins`` ((B, 2) int32 device tensor of (row, column) in frame coordinates, from ``-pad``
