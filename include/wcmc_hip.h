@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define WCMC_ABI_VERSION 2     /* 2: `terms` of the GEMM entry points, packing mode 2 (round 3); round 4 widened the value ranges only (terms = 1, mode 3) */
+#define WCMC_ABI_VERSION 3     /* 2: `terms` of the GEMM entry points, packing mode 2 (round 3); round 4 widened the value ranges only (terms = 1, mode 3)
+                                * 3: the four batch assemblers take `transforms, S_total, s` / `t`: the _prefix and _aug names are gone */
 
 enum wcmc_status {
   WCMC_OK = 0,
@@ -636,11 +637,33 @@ int wcmc_preprocess_kpcn_end(float* out, void* workspace, size_t workspace_bytes
  * per-image buffers kpcn (H, W, 44), llpm (H, W, S, 37; null without --use_llpm_buf) and gt (H, W, 9) and writes the
  * batch dictionary's tensors channel-first and contiguous: diffuse_in / specular_in (B, 34 [+1], P, P), the two
  * 3-channel radiance buffers, albedo + 0.00316, paths (B, S, 36, P, P), and the three targets
- * (total, diffuse / (albedo + 0.00316), log(1 + total - diffuse)).  origins: device int32 [B][2], windows in bounds. */
-int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H,
-                               int W, int S, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
-                               float* specular_buffer, float* albedo, float* paths, float* target_diffuse,
-                               float* target_specular, float* target_total, void* stream);
+ * (total, diffuse / (albedo + 0.00316), log(1 + total - diffuse)).  origins: device int32 [B][2], windows in bounds.
+ * S_total, s (sample counts 2..spp from one staged frame, MSDenoiseDataset :1149-1171): llpm holds S_total samples per pixel and the
+ *   batch takes the first s, 1 <= s <= S_total -- what `llpm[:, :, :s]` feeds __getitem__ (:1045-1118).  paths has s samples; the
+ *   path-weight channel of the two inputs is the mean over the first s, summed in sample order (:1099-1107).  Neither is read
+ *   without llpm (0, 0 will do).
+ * transforms (dihedral patch augmentation): null, or B device ints, one code per patch.  Code t in 0..7 is
+ *   T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) (numpy's rot90 and fliplr on the row and column axes); 0 is the identity,
+ *   and the eight codes are the dihedral group of the square -- what the reference's _random_rot(_random_flip(.))
+ *   (support/datasets.py:718-758) reaches, every element by two of its sixteen draws.  origins keep their meaning: they name a
+ *   P x P window of the source frame, and batch entry b is T_t[b] of that window, as if the whole frame had been transformed
+ *   before preprocessing:
+ *     - every per-pixel channel (values and variances of the five KPCN groups, depth and its variance, path weight, paths, the three
+ *       buffers, albedo, the three targets) is that of the source pixel;
+ *     - the x- and y-differences of the diffuse, specular, normal and albedo values and of the depth are taken again from the stored
+ *       value channels: dx_out(y, x) = val(src(y, x)) - val(src(y, x - 1)), dy_out(y, x) = val(src(y, x)) - val(src(y - 1, x)), one
+ *       fp32 subtraction of two stored floats, where src is the same affine map (at x = 0 / y = 0: one step outside the window), and
+ *       exactly 0.f where that neighbour lies outside the frame (the transformed frame's first column / row, as _gradients);
+ *     - direction-valued channels (normals) are copied, not re-expressed: the reference's functions do the same.
+ *   A null table and a table of zeros give the same batch bit for bit (the null table launches the kernel without the map).  The
+ *   codes are data: the host checks them (ops.check_patch_transforms) and the kernels mask them to t & 7, so a bad table cannot read
+ *   outside the buffers.
+ * WCMC_ERR_BAD_ARG before any launch: a null pointer other than llpm, transforms and paths; a non-positive size; P > H or P > W;
+ *   with llpm, s outside 1..S_total or no paths. */
+int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms,
+                               int B, int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
+                               float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
+                               float* target_diffuse, float* target_specular, float* target_total, void* stream);
 
 /* ---------------------------------------------------------------- patch-sampling probability maps
  * support/datasets.py: gradient_importance_map :17-36 and the `_prob_imp` block of DenoiseDataset._offline_preprocess
@@ -685,73 +708,38 @@ int wcmc_sanitize(float* x, int64_t n, void* stream);
  *   tiled form (1 is an error where the tiled form does not apply); the two forms are bit-identical.
  * wcmc_assemble_sample_patches: the sample-based batch of DenoiseDataset.__getitem__ (:1045-1073, 1086-1118) after _transpose
  *   (:760-791), for B windows of P x P pixels at origins[b] = (row, column) (device int32 [B][2], windows in bounds) of one image:
- *   sbmc_s (H, W, S, 27), sbmc_p (H, W, S, 66; may be null without use_sbmc_buf), llpm (H, W, S, 37) or null, gt (H, W, 9) ->
- *     radiance (B, S, 3, P, P) = sbmc_s 0:3
- *     features (B, S, F, P, P) = [sbmc_s 3:27 if use_g_buf else sbmc_s 3:6] ++ [sbmc_p if use_sbmc_buf] ++ [llpm 0:1 if llpm]
+ *   sbmc_s (H, W, S_total, 27), sbmc_p (H, W, S_total, 66; may be null without use_sbmc_buf), llpm (H, W, S_total, 37) or null,
+ *   gt (H, W, 9); the batch takes the first s samples of each, 1 <= s <= S_total (the `[:, :, :s]` slices of MSDenoiseDataset) ->
+ *     radiance (B, s, 3, P, P) = sbmc_s 0:3
+ *     features (B, s, F, P, P) = [sbmc_s 3:27 if use_g_buf else sbmc_s 3:6] ++ [sbmc_p if use_sbmc_buf] ++ [llpm 0:1 if llpm]
  *                                F = 24 | 3, + 66, + 1
- *     paths    (B, S, 36, P, P) = llpm 1:37 (only with llpm)
+ *     paths    (B, s, 36, P, P) = llpm 1:37 (only with llpm)
  *     target_image (B, 3, P, P) = gt 0:3
- *   One launch; copies only (bit-exact). */
+ *   transforms: null, or one dihedral code per patch as wcmc_assemble_kpcn_patches takes them; every channel is per sample, so every
+ *   one is a copy of the source pixel's (subpixel and light directions included: not re-expressed), and a null table and a table of
+ *   zeros give the same batch.  One launch; copies only (bit-exact).
+ *   WCMC_ERR_BAD_ARG before any launch: a null pointer other than sbmc_p, llpm, transforms and paths; a non-positive size; P > H or
+ *   P > W; s outside 1..S_total; llpm without paths; use_sbmc_buf without sbmc_p. */
 int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples /* h*w*s */, int C, int max_depth, float* out_s, float* out_p,
                          int tiled, void* stream);
 int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                 const int* origins, int B, int H, int W, int S, int P, int use_g_buf, int use_sbmc_buf,
-                                 float* radiance, float* features, float* paths, float* target_image, void* stream);
+                                 const int* origins, const int* transforms, int B, int H, int W, int S_total, int s, int P,
+                                 int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
+                                 float* target_image, void* stream);
 
 /* ---------------------------------------------------------------- sample counts 2..spp from one staged frame (csrc/multi_spp.hip)
  * The reference trains over MSDenoiseDataset (support/datasets.py:1149-1171): one DenoiseDataset per count s = 2..spp, each reading
- * the first s samples of every frame (:618, :1053-1054, :1091).  These entry points get every count out of ONE staged frame.
+ * the first s samples of every frame (:618, :1053-1054, :1091).  Here every count comes out of ONE staged frame.
  * wcmc_preprocess_kpcn_prefix: replaces `_preprocess_kpcn(sample[:, :, :s])` (:487-582) for s = s_lo..s_hi, 1 <= s_lo <= s_hi <=
  *   S <= 64.  raw (h, w, S, C) as for wcmc_preprocess_kpcn -> out (s_hi - s_lo + 1, h, w, 44): slab s - s_lo is what
  *   wcmc_preprocess_kpcn returns for the contiguous first s samples -- mean and population variance over the prefix (:505-543), the
  *   divisions by that s, the depth normalised by that prefix's own image maximum, the gradients of that slab.  Sums run in sample
  *   order (numpy's; wcmc_preprocess_kpcn's for a count that is no power of two), so a power-of-two count may differ from
  *   wcmc_preprocess_kpcn's shuffle tree in the last place.  raw is read from memory once.
- * wcmc_assemble_kpcn_patches_prefix / wcmc_assemble_sample_patches_prefix: wcmc_assemble_kpcn_patches / wcmc_assemble_sample_patches
- *   where llpm, sbmc_s and sbmc_p hold S_total samples per pixel and the batch takes the first s, 1 <= s <= S_total: what
- *   `llpm[:, :, :s]`, `sbmc_s[:, :, :s]`, `sbmc_p[:, :, :s]` feed DenoiseDataset.__getitem__ (:1045-1118).  paths / radiance /
- *   features have s samples; the path-weight channel of the KPCN inputs is the mean over the first s, summed in sample order
- *   (:1099-1107).  s == S_total is the plain entry point bit for bit.  llpm given needs paths (S_total is not read without llpm in
- *   the KPCN form, but must still hold s). */
+ * The batches of a count come from the two patch assemblers above: their S_total / s pair takes the first s of the staged samples. */
 size_t wcmc_preprocess_kpcn_prefix_workspace_bytes(int h, int w, int n_counts);
 int wcmc_preprocess_kpcn_prefix(const float* raw, int h, int w, int S, int C, int max_depth, int s_lo, int s_hi, float* out,
                                 void* workspace, size_t workspace_bytes, void* stream);
-int wcmc_assemble_kpcn_patches_prefix(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B, int H,
-                                      int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
-                                      float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
-                                      float* target_diffuse, float* target_specular, float* target_total, void* stream);
-int wcmc_assemble_sample_patches_prefix(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                        const int* origins, int B, int H, int W, int S_total, int s, int P, int use_g_buf,
-                                        int use_sbmc_buf, float* radiance, float* features, float* paths, float* target_image,
-                                        void* stream);
-
-/* ---------------------------------------------------------------- dihedral patch augmentation
- * wcmc_assemble_kpcn_patches_aug / wcmc_assemble_sample_patches_aug: the `_prefix` entry points with one transform code per patch,
- *   transforms = B device ints.  Code t in 0..7 is T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) (numpy's rot90 and fliplr on
- *   the row and column axes); 0 is the identity, and the eight codes are the dihedral group of the square -- what the reference's
- *   _random_rot(_random_flip(.)) (support/datasets.py:718-758) reaches, every element by two of its sixteen draws.  origins keep
- *   their meaning: they name a P x P window of the source frame, and batch entry b is T_t[b] of that window, as if the whole frame
- *   had been transformed before preprocessing:
- *     - every per-pixel channel (values and variances of the five KPCN groups, depth and its variance, path weight, paths, the three
- *       buffers, albedo, the three targets; every channel of radiance / features / paths / target_image) is that of the source pixel;
- *     - the x- and y-differences of the diffuse, specular, normal and albedo values and of the depth are taken again from the stored
- *       value channels: dx_out(y, x) = val(src(y, x)) - val(src(y, x - 1)), dy_out(y, x) = val(src(y, x)) - val(src(y - 1, x)), one
- *       fp32 subtraction of two stored floats, where src is the same affine map (at x = 0 / y = 0: one step outside the window), and
- *       exactly 0.f where that neighbour lies outside the frame (the transformed frame's first column / row, as _gradients);
- *     - direction-valued channels (normals, subpixel, light directions) are copied, not re-expressed: the reference's functions do the
- *       same.
- *   With all codes 0 the batch is the `_prefix` entry point's bit for bit.  The codes are data: the host checks them (ops.
- *   check_patch_transforms) and the kernels mask them to t & 7, so a bad table cannot read outside the buffers.
- *   WCMC_ERR_BAD_ARG before any launch: null transforms; another null pointer; a non-positive size; P > H or P > W; s outside
- *   1..S_total (pass 1, 1 for a KPCN batch without llpm); llpm without paths; use_sbmc_buf without sbmc_p. */
-int wcmc_assemble_kpcn_patches_aug(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms,
-                                   int B, int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
-                                   float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
-                                   float* target_diffuse, float* target_specular, float* target_total, void* stream);
-int wcmc_assemble_sample_patches_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                     const int* origins, const int* transforms, int B, int H, int W, int S_total, int s, int P,
-                                     int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
-                                     float* target_image, void* stream);
 
 /* ---------------------------------------------------------------- full-frame evaluation
  * The image metrics of the reference's evaluation script (test_models.py:234-251, support/metrics.py) for one
@@ -795,6 +783,16 @@ int wcmc_stitch_tiles(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, i
  *   differences is taken again as value[m(r), m(c)] - value[m(r), m(c - 1)] (rows likewise; 0 at frame position -pad) wherever its two
  *   operands are not in-frame neighbours.  Bit for bit what preprocessing numpy.pad(raw, pad, 'symmetric') and assembling patches at
  *   origins + pad give.  0 <= pad < min(H, W), P > 2*pad, P <= min(H, W) + 2*pad.
+ *   t (dihedral self-ensemble): 0, or a code 1..7 for the tiles of the frame AS IF the raw frame had been
+ *   transformed by T_t before preprocessing.  T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) on the row and column axes, as
+ *   the patch assemblers' codes; the transformed frame is H x W for even t and W x H for odd t, and its pixel (y, x) is source pixel
+ *   (sy, sx) = (y, x), (x, W-1-y), (H-1-y, W-1-x), (H-1-x, y) for k = 0..3, then sx = W-1-sx if t & 4.  One code per launch; H and W
+ *   are always the SOURCE buffers' sizes; origins are in the TRANSFORMED frame's coordinates, and the pad and P conditions hold
+ *   against its sizes.  The mirror is that of the transformed frame, then the map above: copied channels are the source record's
+ *   (direction-valued ones are not re-expressed); each of the 26 differences is value[src(p)] - value[src(p - e)], e one step along
+ *   the transformed frame's x / y, one fp32 subtraction (also of a record with itself), and exactly 0 at the transformed extended
+ *   frame's first column / row.  Bit for bit t = 0 on the buffers preprocessed from the host-transformed raw frame.  t outside 0..7
+ *   is refused on the host and masked in the kernels; every mirrored and mapped index is clamped before use.
  * finish_frame: one pass over the frame after stitching.  out_rad (3, H, W), kpcn (H, W, 44), llpm (H, W, S, 37) ->
  *   ipt (H, W, 3) = kpcn[0:3] * (kpcn[34:37] + 0.00316) + exp(kpcn[10:13]) - 1   (datasets.py:1234)
  *   has_hit (H, W) = 1.0 where (sum over the S samples, in sample order, of llpm[..., 25]) / S != 0, else 0.0   (:1407-1414)
@@ -802,8 +800,8 @@ int wcmc_stitch_tiles(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, i
  *   preview_out / preview_ipt (H, W, 3) uint8, each optional (null: not written): round(255 * clip(tonemap(.), 0, 1)) of out / ipt
  *   with tonemap of test_models.py:24-34 at gamma 1/2.2 on the image's own luminance, rounding half to even; NaN gives 0. */
 int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P, int pad,
-                             float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer, float* albedo,
-                             float* paths, void* stream);
+                             int t, float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer,
+                             float* albedo, float* paths, void* stream);
 int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm, int H, int W, int S, float* out, float* ipt,
                       float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
 
@@ -815,40 +813,26 @@ int wcmc_finish_frame(const float* out_rad, const float* kpcn, const float* llpm
  *   (B, S, 36, P, P), channel for channel as the sample-patch entry point above lays them out (F = 24 | 3, + 66, + 1).  Every buffer
  *   is per sample, so a position outside the frame is a copy of its mirror image's record: bit for bit what preprocessing
  *   numpy.pad(raw, pad, 'symmetric') and assembling sample patches at origins + pad give.  One launch; copies only.
- *   S > 0, 0 <= pad < min(H, W), P > 2*pad, P <= min(H, W) + 2*pad.
+ *   S > 0, 0 <= pad < min(H, W), P > 2*pad, P <= min(H, W) + 2*pad.  t: as assemble_kpcn_tiles takes it -- the frame is read through
+ *   the mirror of the transformed frame and then the same map, the conditions hold against the transformed sizes; copies only.
  * finish_sample_frame (csrc/frame_tiles.hip): finish_frame with the noisy input of the sample-based models,
  *   ipt (H, W, 3) = (sum over the S samples, in sample order, of sbmc_s[..., 0:3]) / S   (datasets.py:1248)
  *   has_hit, out and the two optional previews as finish_frame. */
 int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B, int H, int W,
-                               int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
+                               int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf, float* radiance, float* features,
                                float* paths, void* stream);
 int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_s, const float* llpm, int H, int W, int S, float* out,
                              float* ipt, float* has_hit, unsigned char* preview_out, unsigned char* preview_ipt, void* stream);
 
 /* ---------------------------------------------------------------- dihedral self-ensemble of a frame
- * The tile batches of the frame AS IF the raw frame had been transformed by T_t before preprocessing, and the way back.  Code t in
- * 0..7 is that of the `_aug` patch entry points: T_t(a) = rot90(fliplr(a) if t & 4 else a, k = t & 3) on the row and column axes;
- * the transformed frame is H x W for even t and W x H for odd t, and its pixel (y, x) is source pixel (sy, sx) = (y, x),
- * (x, W-1-y), (H-1-y, W-1-x), (H-1-x, y) for k = 0..3, then sx = W-1-sx if t & 4.  One code per launch; H and W are always the
- * SOURCE buffers' sizes; origins and coords are in the TRANSFORMED frame's coordinates.  t outside 0..7 is refused on the host and
- * masked in the kernels; every mirrored and mapped index is clamped before use.
- * assemble_kpcn_tiles_aug: assemble_kpcn_tiles through the mirror of the transformed frame and then the map above.  Copied channels
- *   are the source record's (direction-valued ones are not re-expressed); each of the 26 differences is
- *   value[src(p)] - value[src(p - e)], e one step along the transformed frame's x / y, one fp32 subtraction (also of a record with
- *   itself), and exactly 0 at the transformed extended frame's first column / row.  Bit for bit assemble_kpcn_tiles on the buffers
- *   preprocessed from the host-transformed raw frame.  pad and P conditions as the plain entry point's, against the transformed sizes.
- * assemble_sample_tiles_aug (csrc/sbmc_data.hip): assemble_sample_tiles through the same composed map; copies only.
+ * The way back of a pass whose tiles were assembled under a code t (assemble_kpcn_tiles / assemble_sample_tiles above: the code, the
+ * transformed frame's sizes and the source map (sy, sx) of its pixel (y, x) are defined there).  coords are in the TRANSFORMED
+ * frame's coordinates; t outside 0..7 is refused on the host and masked in the kernel.
  * stitch_tiles_aug: for every tile b with coords[b] = (i_start, j_start, i_end, j_end, i, j) of the transformed frame's table (device
  *   int32 (B, 6)) and every pixel (y, x) of its owned window, v = rad (B, 3, ho, wo) 'replicate'-padded back to P x P as stitch_tiles
  *   does it, and out_rad[:, sy, sx] = v (accumulate = 0) or out_rad[:, sy, sx] + v (accumulate = 1); out_rad (3, H, W) contiguous, in
  *   SOURCE orientation.  The owned windows partition the frame, so a launch set touches every element once: no atomics, and passes
  *   that follow one another on one stream give a bit-defined sum.  No P-buffers (those are the identity pass's). */
-int wcmc_assemble_kpcn_tiles_aug(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P, int pad,
-                                 int t, float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer,
-                                 float* albedo, float* paths, void* stream);
-int wcmc_assemble_sample_tiles_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B, int H,
-                                   int W, int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf, float* radiance,
-                                   float* features, float* paths, void* stream);
 int wcmc_stitch_tiles_aug(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,
                           const int* coords, int B, int t, int H, int W, int accumulate, float* out_rad, void* stream);
 

@@ -1,5 +1,5 @@
-"""Dihedral patch augmentation without a GPU: the two `_aug` entry points in the header, the binding and the
-built library; their argument checks (which precede any HIP call); the host check of a code table; the eight codes against the
+"""Dihedral patch augmentation without a GPU: the two patch entry points, which take the code table, in the
+header, the binding and the built library; their argument checks (which precede any HIP call); the host check of a code table; the eight codes against the
 reference's flip-then-rotate draws; the loader's private draw; the launchers' argument errors."""
 import ctypes
 import itertools
@@ -11,7 +11,12 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("wcmc_assemble_kpcn_patches_aug", "wcmc_assemble_sample_patches_aug")
+NEW = {"wcmc_assemble_kpcn_patches": 21, "wcmc_assemble_sample_patches": 19}
+# ABI 3 folded the variants of the four batch assemblers into the base names: these six are gone
+GONE = tuple(base + suffix for base, suffixes in (("wcmc_assemble_kpcn_patches", ("_prefix", "_aug")),
+                                                  ("wcmc_assemble_sample_patches", ("_prefix", "_aug")),
+                                                  ("wcmc_assemble_kpcn_tiles", ("_aug",)), ("wcmc_assemble_sample_tiles", ("_aug",)))
+             for suffix in suffixes)
 
 
 def T(a, t):
@@ -27,14 +32,17 @@ def test_new_symbols_are_declared_bound_and_exported():
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     declared = set(re.findall(r"\b(wcmc_[a-z0-9_]+)\s*\(", header))
     h = lib()
-    for name in NEW:
+    for name, nargs in NEW.items():
         assert name in declared and name in SIGNATURES, name
         assert getattr(h, name) is not None
         m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, header, flags=re.S)
-        assert len(m.group(1).split(",")) == len(SIGNATURES[name][1]), name
-        # the `_prefix` entry point's arguments plus the table
-        pre = name.replace("_aug", "_prefix")
-        assert len(SIGNATURES[name][1]) == len(SIGNATURES[pre][1]) + 1, name
+        # the buffers, the origins and the table, B H W S_total s P, the flags of the sample form, the outputs, the stream
+        assert len(m.group(1).split(",")) == len(SIGNATURES[name][1]) == nargs, name
+    assert len(GONE) == 6
+    for name in GONE:
+        assert name not in declared and name not in SIGNATURES, name
+        with pytest.raises(AttributeError):
+            getattr(h, name)
 
 
 def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
@@ -47,21 +55,24 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
 
     def kpcn(**kw):
         a = dict(good, **kw)
-        return L.wcmc_assemble_kpcn_patches_aug(a["a"], a["llpm"], a["gt"], a["origins"], a["tr"], a["B"], a["H"], a["W"], a["S"], a["s"],
-                                                a["P"], a["out"], one, one, one, one, a["paths"], one, one, one, null)
+        return L.wcmc_assemble_kpcn_patches(a["a"], a["llpm"], a["gt"], a["origins"], a["tr"], a["B"], a["H"], a["W"], a["S"], a["s"],
+                                            a["P"], a["out"], one, one, one, one, a["paths"], one, one, one, null)
 
     def sample(**kw):
         a = dict(good, **kw)
-        return L.wcmc_assemble_sample_patches_aug(a["a"], a["sbmc_p"], a["llpm"], a["gt"], a["origins"], a["tr"], a["B"], a["H"], a["W"],
-                                                  a["S"], a["s"], a["P"], 1, a["use_p"], a["out"], one, a["paths"], one, null)
-    shared = {"null transforms": (dict(tr=null), "null transforms"), "s = 0": (dict(s=0), "1 <= s <= S_total"),
+        return L.wcmc_assemble_sample_patches(a["a"], a["sbmc_p"], a["llpm"], a["gt"], a["origins"], a["tr"], a["B"], a["H"], a["W"],
+                                              a["S"], a["s"], a["P"], 1, a["use_p"], a["out"], one, a["paths"], one, null)
+    # (a null table is the plain batch, not an error: with it a bad argument is still refused, by the same check and with the sizes
+    # it was given -- the KPCN form has five kinds of refusal since the null table stopped being one, this entry holds the numbers)
+    shared = {"null transforms, P > H": (dict(tr=null, P=25), "a 25-pixel patch does not fit the 24 x 40 frame"),
+              "s = 0": (dict(s=0), "1 <= s <= S_total"),
               "s > S_total": (dict(s=4), "1 <= s <= S_total"), "S_total = 0": (dict(S=0, s=0), "1 <= s <= S_total"),
               "P > H": (dict(P=25), "does not fit"), "P > W": (dict(H=64, P=41), "does not fit"), "P = 0": (dict(P=0), "must be positive"),
               "B = 0": (dict(B=0), "must be positive"), "null buffer": (dict(a=null), "null pointer"),
               "null gt": (dict(gt=null), "null pointer"), "null origins": (dict(origins=null), "null pointer"),
               "null output": (dict(out=null), "null pointer"), "llpm without paths": (dict(paths=null), "without a paths output")}
-    for fn, op, extra in ((kpcn, "assemble_kpcn_patches_aug", {}),
-                          (sample, "assemble_sample_patches_aug", {"use_sbmc_buf without sbmc_p": (dict(sbmc_p=null), "needs sbmc_p")})):
+    for fn, op, extra in ((kpcn, "assemble_kpcn_patches", {}),
+                          (sample, "assemble_sample_patches", {"use_sbmc_buf without sbmc_p": (dict(sbmc_p=null), "needs sbmc_p")})):
         seen = set()
         for what, (kw, word) in dict(shared, **extra).items():
             assert fn(**kw) == -1, (op, what)                                    # WCMC_ERR_BAD_ARG
@@ -69,8 +80,10 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
             assert msg.startswith(op + ":") and word in msg, (op, what, msg)
             seen.add(word)
         assert len(seen) >= 6                                                    # each kind of refusal has its own message
-    # a null transforms is not mistaken for the plain entry point's call
-    assert kpcn(tr=null, llpm=null, paths=null) == -1 and "assemble_kpcn_patches_aug" in L.wcmc_last_error().decode()
+    # ... also without llpm, where the KPCN form reads neither sample count (S_total = s = 0 is what ops passes then)
+    assert kpcn(tr=null, llpm=null, paths=null, S=0, s=0, P=25) == -1
+    msg = L.wcmc_last_error().decode()
+    assert msg.startswith("assemble_kpcn_patches:") and "does not fit" in msg, msg
 
 
 def test_check_patch_transforms_refuses_length_dtype_and_range():

@@ -54,9 +54,9 @@ def test_new_entry_points_reject_bad_arguments_without_touching_the_gpu():
     L = _lib.lib()
     null, one = ctypes.c_void_p(0), ctypes.c_void_p(256)          # `one`: non-null, aligned, never dereferenced by the checks
     tiles = lambda **kw: L.wcmc_assemble_kpcn_tiles(*[{**dict(   # noqa: E731
-        kpcn=one, llpm=null, origins=one, B=2, H=70, W=83, S=0, P=128, pad=32, din=one, sin=one, dbuf=one, sbuf=one, alb=one,
-        paths=null, stream=null), **kw}[k] for k in ("kpcn", "llpm", "origins", "B", "H", "W", "S", "P", "pad", "din", "sin", "dbuf",
-                                                     "sbuf", "alb", "paths", "stream")])
+        kpcn=one, llpm=null, origins=one, B=2, H=70, W=83, S=0, P=128, pad=32, t=0, din=one, sin=one, dbuf=one, sbuf=one, alb=one,
+        paths=null, stream=null), **kw}[k] for k in ("kpcn", "llpm", "origins", "B", "H", "W", "S", "P", "pad", "t", "din", "sin",
+                                                     "dbuf", "sbuf", "alb", "paths", "stream")])
     finish = lambda **kw: L.wcmc_finish_frame(*[{**dict(   # noqa: E731
         out_rad=one, kpcn=one, llpm=one, H=70, W=83, S=2, out=one, ipt=one, has_hit=one, pv_out=null, pv_ipt=null, stream=null),
         **kw}[k] for k in ("out_rad", "kpcn", "llpm", "H", "W", "S", "out", "ipt", "has_hit", "pv_out", "pv_ipt", "stream")])
@@ -67,6 +67,7 @@ def test_new_entry_points_reject_bad_arguments_without_touching_the_gpu():
              (tiles, dict(H=32), "pad = 32 must be smaller"), (tiles, dict(W=20), "pad = 32 must be smaller"),
              (tiles, dict(P=64), "no interior"), (tiles, dict(P=63), "no interior"),
              (tiles, dict(H=40, W=40, P=128), "does not fit"), (tiles, dict(B=0), "positive"), (tiles, dict(pad=-1), "non-negative"),
+             (tiles, dict(t=8), "0..7"),
              (finish, dict(out_rad=null), "null pointer"), (finish, dict(kpcn=null), "null pointer"),
              (finish, dict(llpm=null), "null pointer"), (finish, dict(has_hit=null), "null pointer"),
              (finish, dict(S=0), "must be positive"), (finish, dict(H=0), "must be positive")]

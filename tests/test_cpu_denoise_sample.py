@@ -11,10 +11,10 @@ def test_new_entry_points_reject_bad_arguments_without_touching_the_gpu():
     from wcmc_amd import _lib
     L = _lib.lib()
     null, one = ctypes.c_void_p(0), ctypes.c_void_p(256)          # `one`: non-null, aligned, never dereferenced by the checks
-    tile_keys = ("sbmc_s", "sbmc_p", "llpm", "origins", "B", "H", "W", "S", "P", "pad", "g", "p", "rad", "feat", "paths", "stream")
+    tile_keys = ("sbmc_s", "sbmc_p", "llpm", "origins", "B", "H", "W", "S", "P", "pad", "t", "g", "p", "rad", "feat", "paths", "stream")
     tiles = lambda **kw: L.wcmc_assemble_sample_tiles(*[{**dict(   # noqa: E731
-        sbmc_s=one, sbmc_p=one, llpm=one, origins=one, B=2, H=70, W=83, S=2, P=128, pad=32, g=1, p=1, rad=one, feat=one, paths=one,
-        stream=null), **kw}[k] for k in tile_keys])
+        sbmc_s=one, sbmc_p=one, llpm=one, origins=one, B=2, H=70, W=83, S=2, P=128, pad=32, t=0, g=1, p=1, rad=one, feat=one,
+        paths=one, stream=null), **kw}[k] for k in tile_keys])
     fin_keys = ("out_rad", "sbmc_s", "llpm", "H", "W", "S", "out", "ipt", "has_hit", "pv_out", "pv_ipt", "stream")
     finish = lambda **kw: L.wcmc_finish_sample_frame(*[{**dict(   # noqa: E731
         out_rad=one, sbmc_s=one, llpm=one, H=70, W=83, S=2, out=one, ipt=one, has_hit=one, pv_out=null, pv_ipt=null, stream=null),
@@ -26,7 +26,7 @@ def test_new_entry_points_reject_bad_arguments_without_touching_the_gpu():
              (tiles, dict(S=0), "S must be positive"), (tiles, dict(S=-3), "S must be positive"),
              (tiles, dict(P=64), "no interior"), (tiles, dict(P=63), "no interior"), (tiles, dict(pad=64), "no interior"),
              (tiles, dict(H=32), "pad = 32 must be smaller"), (tiles, dict(H=40, W=40), "does not fit"),
-             (tiles, dict(B=0), "positive"), (tiles, dict(pad=-1), "non-negative"),
+             (tiles, dict(B=0), "positive"), (tiles, dict(pad=-1), "non-negative"), (tiles, dict(t=8), "0..7"),
              (finish, dict(out_rad=null), "null pointer"), (finish, dict(sbmc_s=null), "null pointer"),
              (finish, dict(llpm=null), "null pointer"), (finish, dict(ipt=null), "null pointer"),
              (finish, dict(S=0), "must be positive"), (finish, dict(W=0), "must be positive")]

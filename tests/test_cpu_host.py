@@ -41,7 +41,7 @@ def test_library_exports_every_declared_symbol():
     h = lib()
     for name in declared:
         assert getattr(h, name) is not None
-    assert h.wcmc_abi_version() == 2
+    assert h.wcmc_abi_version() == 3
     # pure host-side size queries work without a GPU
     assert h.wcmc_conv2d_packed_elems(100, 100, 5) == 112 * 2528
     assert h.wcmc_conv2d_packed_elems(441, 100, 5) == 448 * 2528
@@ -85,7 +85,7 @@ def test_abi_rejects_bad_arguments_without_touching_the_gpu():
         "wcmc_conv1x1_pair_bf16x3": (one, 1, 8, 8, 100, one, null, 128, 1, 0.0, one, null, null, 0, 0.0, null, one, null, 3,
                                      1, 0.0, one, 256, 32, 4, null),
         "wcmc_sample_cat_fwd": (one, 1, 1, 1, 1, 1, one, 1, 1, 1, 1, 1, one, 2, 1, 4, 3, 8, 8, null),     # S = 1: no variance
-        "wcmc_assemble_kpcn_patches": (one, null, one, one, 2, 16, 16, 0, 32, one, one, one, one, one, null, one, one, one,
+        "wcmc_assemble_kpcn_patches": (one, null, one, one, null, 2, 16, 16, 0, 0, 32, one, one, one, one, one, null, one, one, one,
                                        null),                                                      # patch larger than the image
     }
     for name, args in cases.items():

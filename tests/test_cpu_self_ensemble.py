@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"wcmc_assemble_kpcn_tiles_aug": "wcmc_assemble_kpcn_tiles", "wcmc_assemble_sample_tiles_aug": "wcmc_assemble_sample_tiles",
-       "wcmc_stitch_tiles_aug": None}
+NEW = {"wcmc_stitch_tiles_aug": 16, "wcmc_assemble_kpcn_tiles": 17, "wcmc_assemble_sample_tiles": 17}
 PATCH, PAD = 128, 32
 SIZES = [(64, 64), (70, 83), (128, 150)]
 
@@ -39,14 +38,11 @@ def test_new_symbols_are_declared_bound_and_exported():
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     declared = set(re.findall(r"\b(wcmc_[a-z0-9_]+)\s*\(", header))
     h = lib()
-    for name, plain in NEW.items():
+    for name, nargs in NEW.items():                              # (the two tile assemblers: the code t behind pad)
         assert name in declared and name in SIGNATURES, name
         assert getattr(h, name) is not None
         m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, header, flags=re.S)
-        assert len(m.group(1).split(",")) == len(SIGNATURES[name][1]), name
-        if plain:                                                # the plain entry point's arguments plus the code
-            assert len(SIGNATURES[name][1]) == len(SIGNATURES[plain][1]) + 1, name
-    assert len(SIGNATURES["wcmc_stitch_tiles_aug"][1]) == 16
+        assert len(m.group(1).split(",")) == len(SIGNATURES[name][1]) == nargs, name
 
 
 def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
@@ -59,22 +55,22 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
 
     def kpcn(**kw):
         a = dict(good, **kw)
-        return L.wcmc_assemble_kpcn_tiles_aug(a["a"], a["llpm"], a["org"], a["B"], a["H"], a["W"], a["S"], a["P"], a["pad"], a["t"],
-                                              a["out"], one, one, one, one, a["paths"], null)
+        return L.wcmc_assemble_kpcn_tiles(a["a"], a["llpm"], a["org"], a["B"], a["H"], a["W"], a["S"], a["P"], a["pad"], a["t"],
+                                          a["out"], one, one, one, one, a["paths"], null)
 
     def sample(**kw):
         a = dict(good, **kw)
-        return L.wcmc_assemble_sample_tiles_aug(a["a"], a["sbmc_p"], a["llpm"], a["org"], a["B"], a["H"], a["W"], a["S"], a["P"],
-                                                a["pad"], a["t"], 1, a["use_p"], a["out"], one, a["paths"], null)
+        return L.wcmc_assemble_sample_tiles(a["a"], a["sbmc_p"], a["llpm"], a["org"], a["B"], a["H"], a["W"], a["S"], a["P"],
+                                            a["pad"], a["t"], 1, a["use_p"], a["out"], one, a["paths"], null)
     shared = {"t = 8": (dict(t=8), "0..7"), "t = -1": (dict(t=-1), "0..7"), "null buffer": (dict(a=null), "null pointer"),
               "null origins": (dict(org=null), "null pointer"), "null output": (dict(out=null), "null pointer"),
               "llpm without paths": (dict(paths=null), "paths output"), "B = 0": (dict(B=0), "must be positive"),
               "H = 0": (dict(H=0), "must be positive"), "P = 0": (dict(P=0), "must be positive"),
               "negative pad": (dict(pad=-1), "pad non-negative"), "pad >= a side": (dict(H=32), "one reflection"),
               "no interior": (dict(P=64), "no interior"), "tile too large": (dict(H=60, W=60), "does not fit")}
-    for fn, op, extra in ((kpcn, "assemble_kpcn_tiles_aug", {"llpm with S = 0": (dict(S=0), "S > 0")}),
-                          (sample, "assemble_sample_tiles_aug", {"use_sbmc_buf without sbmc_p": (dict(sbmc_p=null), "needs sbmc_p"),
-                                                                 "S = 0": (dict(S=0), "S must be positive")})):
+    for fn, op, extra in ((kpcn, "assemble_kpcn_tiles", {"llpm with S = 0": (dict(S=0), "S > 0")}),
+                          (sample, "assemble_sample_tiles", {"use_sbmc_buf without sbmc_p": (dict(sbmc_p=null), "needs sbmc_p"),
+                                                             "S = 0": (dict(S=0), "S must be positive")})):
         seen = set()
         assert set(dict(shared, **extra)) > set(shared)
         for what, (kw, word) in dict(shared, **extra).items():
@@ -86,6 +82,9 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     # the pad / P conditions are taken against the TRANSFORMED sizes: the message names them turned for an odd code
     assert kpcn(H=60, W=200, t=1) == -1 and "transformed 200 x 60 frame" in L.wcmc_last_error().decode()
     assert kpcn(H=60, W=200, t=2) == -1 and "transformed 60 x 200 frame" in L.wcmc_last_error().decode()
+    # ... and t = 0 is the frame as it is: the untransformed sizes
+    for fn in (kpcn, sample):
+        assert fn(H=60, W=200, t=0) == -1 and "does not fit the transformed 60 x 200 frame" in L.wcmc_last_error().decode()
 
     sgood = dict(rad=one, ho=92, wo=92, P=128, coords=one, B=2, t=5, H=70, W=83, acc=1, out=one)
 

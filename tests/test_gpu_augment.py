@@ -1,5 +1,5 @@
-"""GPU tests of the dihedral patch augmentation in the device patch assemblers (``wcmc_assemble_kpcn_patches_aug``
-and ``wcmc_assemble_sample_patches_aug``).  Everything is held to ``torch.equal``: the per-pixel channels are copies and every
+"""GPU tests of the dihedral patch augmentation in the device patch assemblers (``wcmc_assemble_kpcn_patches``
+and ``wcmc_assemble_sample_patches`` with a code table).  Everything is held to ``torch.equal``: the per-pixel channels are copies and every
 retaken difference is one fp32 subtraction of two stored floats.
 
 Where a source pixel lies is never computed from the formulas of the specification here: an index image of the frame goes through

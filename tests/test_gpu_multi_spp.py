@@ -157,17 +157,19 @@ def test_prefix_assembly_rejects_bad_arguments_through_the_abi(buffers):
     o = ptr(out)
 
     def kpcn(s_total, s, paths):
-        return L.wcmc_assemble_kpcn_patches_prefix(ptr(b["kpcn"]), ptr(b["llpm"]), ptr(b["gt"]), ptr(b["origins"]), 3, H, W, s_total, s,
-                                                   P, o, o, o, o, o, paths, o, o, o, null)
+        return L.wcmc_assemble_kpcn_patches(ptr(b["kpcn"]), ptr(b["llpm"]), ptr(b["gt"]), ptr(b["origins"]), null, 3, H, W, s_total, s,
+                                            P, o, o, o, o, o, paths, o, o, o, null)
 
     def sample(s_total, s, paths):
-        return L.wcmc_assemble_sample_patches_prefix(ptr(b["sbmc_s"]), ptr(b["sbmc_p"]), ptr(b["llpm"]), ptr(b["gt"]), ptr(b["origins"]),
-                                                     3, H, W, s_total, s, P, 1, 1, o, o, paths, o, null)
+        return L.wcmc_assemble_sample_patches(ptr(b["sbmc_s"]), ptr(b["sbmc_p"]), ptr(b["llpm"]), ptr(b["gt"]), ptr(b["origins"]), null,
+                                              3, H, W, s_total, s, P, 1, 1, o, o, paths, o, null)
 
-    for fn, name in ((kpcn, "assemble_kpcn_patches_prefix"), (sample, "assemble_sample_patches_prefix")):
-        for args in ((S_TOTAL, 0, o), (S_TOTAL, S_TOTAL + 1, o), (S_TOTAL, 2, null)):
+    for fn, name in ((kpcn, "assemble_kpcn_patches"), (sample, "assemble_sample_patches")):    # (a null table: the plain batch)
+        for args, word in (((S_TOTAL, 0, o), "1 <= s <= S_total"), ((S_TOTAL, S_TOTAL + 1, o), "1 <= s <= S_total"),
+                           ((0, 0, o), "1 <= s <= S_total"), ((S_TOTAL, 2, null), "without a paths output")):
             assert fn(*args) == -1, (name, args)                                          # WCMC_ERR_BAD_ARG
-            assert name in L.wcmc_last_error().decode()
+            msg = L.wcmc_last_error().decode()
+            assert msg.startswith(name + ":") and word in msg, (name, args, msg)
     torch.cuda.synchronize()
     from wcmc_amd import ops
     with pytest.raises(ValueError, match="prefix"):

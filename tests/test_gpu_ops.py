@@ -44,7 +44,7 @@ def gen(*shape, seed=0, scale=1.0):
 
 def test_library_loaded_is_in_tree():
     from wcmc_amd._lib import LIB_PATH, lib
-    assert lib().wcmc_abi_version() == 2
+    assert lib().wcmc_abi_version() == 3
     assert os.path.isfile(LIB_PATH)
     with open("/proc/self/maps") as f:
         assert "libwcmc_hip.so" in f.read()

@@ -1,5 +1,5 @@
 """The dihedral self-ensemble of wcmc_amd.denoise on the GPU (csrc/frame_tiles.hip:
-wcmc_assemble_kpcn_tiles_aug, wcmc_stitch_tiles_aug; csrc/sbmc_data.hip: wcmc_assemble_sample_tiles_aug;
+wcmc_stitch_tiles_aug, wcmc_assemble_kpcn_tiles with a code t; csrc/sbmc_data.hip: wcmc_assemble_sample_tiles with a code t;
 support.inference.denoise_frame / denoise_sample_frame with ``ensemble``; ``--self_ensemble``).
 
 The tile batches under a code are held bit for bit against the route that exists without them -- the plain tile assemblers on the

@@ -122,7 +122,7 @@ SIGNATURES = {
     "wcmc_preprocess_kpcn_rows": (I, [P, I, I, I, I, I, I, I, P, P, Z, P]),
     "wcmc_preprocess_kpcn_end": (I, [P, P, Z, I, I, I, P]),
     "wcmc_gradients": (I, [P, I, I, I, P, P]),
-    "wcmc_assemble_kpcn_patches": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "wcmc_assemble_kpcn_patches": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "wcmc_reflect_index": (I, [I, I]),
     "wcmc_importance_map_workspace_bytes": (Z, [I, I, I]),
     "wcmc_importance_map": (I, [P, I, I, I, P, P, Z, P]),
@@ -130,22 +130,16 @@ SIGNATURES = {
     "wcmc_sampling_prob": (I, [P, P, I, I, I, I, I, I, P, P, Z, P]),
     "wcmc_sanitize": (I, [P, L, P]),
     "wcmc_preprocess_sbmc": (I, [P, L, I, I, P, P, I, P]),
-    "wcmc_assemble_sample_patches": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "wcmc_assemble_sample_patches": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
     "wcmc_preprocess_kpcn_prefix_workspace_bytes": (Z, [I, I, I]),
     "wcmc_preprocess_kpcn_prefix": (I, [P, I, I, I, I, I, I, I, P, P, Z, P]),
-    "wcmc_assemble_kpcn_patches_prefix": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "wcmc_assemble_sample_patches_prefix": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
-    "wcmc_assemble_kpcn_patches_aug": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "wcmc_assemble_sample_patches_aug": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P]),
     "wcmc_image_eval_workspace_bytes": (Z, [I, I]),
     "wcmc_image_eval": (I, [P, L, L, L, P, L, L, L, P, L, L, L, P, L, L, L, I, I, D, P, P, Z, P]),
     "wcmc_stitch_tiles": (I, [P, L, L, L, L, I, I, P, P, I, I, I, P, I, I, I, P, P, P, P]),
-    "wcmc_assemble_kpcn_tiles": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P]),
+    "wcmc_assemble_kpcn_tiles": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P]),
     "wcmc_finish_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
-    "wcmc_assemble_sample_tiles": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P]),
+    "wcmc_assemble_sample_tiles": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
     "wcmc_finish_sample_frame": (I, [P, P, P, I, I, I, P, P, P, P, P, P]),
-    "wcmc_assemble_kpcn_tiles_aug": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P]),
-    "wcmc_assemble_sample_tiles_aug": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
     "wcmc_stitch_tiles_aug": (I, [P, L, L, L, L, I, I, I, P, I, I, I, I, I, P, P]),
     "wcmc_stitch_tiles_blend": (I, [P, L, L, L, L, I, I, I, I, P, I, I, I, I, I, P, P, P]),
     "wcmc_blend_finish": (I, [P, P, I, I, I, P, P]),
@@ -168,7 +162,7 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
-        if h.wcmc_abi_version() != 2:
+        if h.wcmc_abi_version() != 3:
             raise RuntimeError("wcmc_amd: ABI version mismatch in %s" % LIB_PATH)
         _lib = h
     return _lib

@@ -1,6 +1,6 @@
 // What the data-step translation units share (preprocess.hip, multi_spp.hip, sbmc_data.hip, frame_tiles.hip): the raw channel map, the layout of
-// the 44-channel KPCN buffer, the per-sample values and per-pixel closing arithmetic of _preprocess_kpcn, the finish pass, and
-// the host launchers of the two patch-assembly kernels (each kernel lives in ONE unit; the other unit calls its launcher).
+// the 44-channel KPCN buffer, the per-sample values and per-pixel closing arithmetic of _preprocess_kpcn, the finish pass, the
+// mirror map and the dihedral maps of the assembly kernels.
 #pragma once
 #include "common.h"
 
@@ -166,16 +166,5 @@ __device__ __forceinline__ FramePos frame_map(int t, int y, int x, int H, int W)
   m.sx = min(max(m.sx, 0), W - 1);
   return m;
 }
-
-// Launchers of the patch-assembly kernels (preprocess.hip, sbmc_data.hip).  The per-sample buffers hold S_total samples per pixel,
-// the outputs the first s of them; the arguments have been validated by the entry point that calls.  transforms: null launches the
-// plain kernel; B device ints launch the instantiation that applies patch_map (the `_aug` entry points).
-int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms, int B,
-                            int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
-                            float* specular_buffer, float* albedo, float* paths, float* target_diffuse, float* target_specular,
-                            float* target_total, hipStream_t stream);
-int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins,
-                       const int* transforms, int B, int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf,
-                       float* radiance, float* features, float* paths, float* target_image, hipStream_t stream);
 
 }  // namespace wcmc

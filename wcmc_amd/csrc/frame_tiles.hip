@@ -8,8 +8,8 @@
 //                             the edge.  Bit for bit what preprocessing the padded raw frame and wcmc_assemble_kpcn_patches give.
 //   wcmc_finish_frame         one pass over the stitched frame: the noisy input, the has-hit mask, the composite and 8-bit previews.
 // The dihedral self-ensemble adds the way through a whole-frame transform and back:
-//   wcmc_assemble_kpcn_tiles_aug  the same batch of the frame as if the RAW frame had been flipped / turned before preprocessing.
-//   wcmc_stitch_tiles_aug         pastes or adds the owned windows of the transformed frame's tiles into the frame in source orientation.
+//   wcmc_assemble_kpcn_tiles, t > 0   the same batch of the frame as if the RAW frame had been flipped / turned before preprocessing.
+//   wcmc_stitch_tiles_aug             pastes or adds the owned windows of the transformed frame's tiles into the frame in source orientation.
 // Feathered seams:
 //   wcmc_stitch_tiles_blend       adds w * v and w of one batch of tiles, each on its owned window widened by F pixels, under a code t.
 //   wcmc_blend_finish             out = acc / wsum, or out += acc / wsum: a pass normalised by its own weight sum.
@@ -24,7 +24,7 @@ struct TileOut {
 // (ft_grad_src / ft_grad_dst, the channels of the backward differences, are in data_step.h: the augmented patch assembler uses them too)
 // One thread per (tile, y, x), as pp_assemble_kpcn_kernel: every output plane is written as coalesced rows, each record is read once
 // (a second record's thirteen values only where a difference crosses the frame's edge: the outer `pad` ring of border tiles).
-// AUG (the `_aug` entry point): the whole launch reads the frame through one dihedral transform t.  The origins
+// AUG (a code t in 1..7): the whole launch reads the frame through one dihedral transform t.  The origins
 // and the mirror are those of the TRANSFORMED frame (Ht x Wt: W x H for odd t), frame_map then gives the source record, and each of the
 // 26 differences is value[src(p)] - value[src(p - e)] with e one step along the transformed frame's x / y.  Where that neighbour's
 // source is the stored one (one column / row before the source) the stored difference is that very subtraction and is kept; elsewhere
@@ -370,55 +370,34 @@ extern "C" int wcmc_finish_sample_frame(const float* out_rad, const float* sbmc_
 }
 
 extern "C" int wcmc_assemble_kpcn_tiles(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P,
-                                        int pad, float* diffuse_in, float* specular_in, float* diffuse_buffer,
+                                        int pad, int t, float* diffuse_in, float* specular_in, float* diffuse_buffer,
                                         float* specular_buffer, float* albedo, float* paths, void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: the transform code must lie in 0..7 (got %d)", t);
   WCMC_REQUIRE(kpcn && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo, WCMC_ERR_BAD_ARG,
                "assemble_kpcn_tiles: null pointer");
   WCMC_REQUIRE(!llpm || (paths && S > 0), WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: llpm needs a paths output and S > 0");
   WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
                "assemble_kpcn_tiles: B, H, W, P must be positive and pad non-negative");
-  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
-  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
-  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
-  TileOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths};
-  const int64_t total = (int64_t)B * P * P;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-  if (aligned16(kpcn))
-    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
-                       B, H, W, S, P, pad, 0);
-  else
-    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
-                       B, H, W, S, P, pad, 0);
-  return check_launch("assemble_kpcn_tiles");
-}
-
-extern "C" int wcmc_assemble_kpcn_tiles_aug(const float* kpcn, const float* llpm, const int* origins, int B, int H, int W, int S, int P,
-                                            int pad, int t, float* diffuse_in, float* specular_in, float* diffuse_buffer,
-                                            float* specular_buffer, float* albedo, float* paths, void* stream) {
-  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: the transform code must lie in 0..7 (got %d)", t);
-  WCMC_REQUIRE(kpcn && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles_aug: null pointer");
-  WCMC_REQUIRE(!llpm || (paths && S > 0), WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: llpm needs a paths output and S > 0");
-  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles_aug: B, H, W, P must be positive and pad non-negative");
   const int Ht = t & 1 ? W : H, Wt = t & 1 ? H : W;
   WCMC_REQUIRE(pad < Ht && pad < Wt, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles_aug: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
-  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles_aug: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+               "assemble_kpcn_tiles: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_kpcn_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
   WCMC_REQUIRE(P <= Ht + 2 * pad && P <= Wt + 2 * pad, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_tiles_aug: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
+               "assemble_kpcn_tiles: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
   TileOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths};
   const int64_t total = (int64_t)B * P * P;
-  const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-  if (aligned16(kpcn))
-    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o, B,
-                       H, W, S, P, pad, t);
+  const dim3 grid((unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535));
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = aligned16(kpcn);
+  if (vec && t)
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, true>), grid, dim3(256), 0, st, kpcn, llpm, origins, o, B, H, W, S, P, pad, t);
+  else if (t)
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, true>), grid, dim3(256), 0, st, kpcn, llpm, origins, o, B, H, W, S, P, pad, t);
+  else if (vec)
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<true, false>), grid, dim3(256), 0, st, kpcn, llpm, origins, o, B, H, W, S, P, pad, 0);
   else
-    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, origins, o,
-                       B, H, W, S, P, pad, t);
-  return check_launch("assemble_kpcn_tiles_aug");
+    hipLaunchKernelGGL((ft_assemble_tiles_kernel<false, false>), grid, dim3(256), 0, st, kpcn, llpm, origins, o, B, H, W, S, P, pad, 0);
+  return check_launch("assemble_kpcn_tiles");
 }
 
 extern "C" int wcmc_stitch_tiles_aug(const float* rad, int64_t rsb, int64_t rsc, int64_t rsh, int64_t rsw, int ho, int wo, int P,

@@ -3,8 +3,8 @@
 // The reference trains over MSDenoiseDataset (support/datasets.py:1149-1171): one DenoiseDataset per count s = 2..spp, each of
 // which reads the first s samples of every frame (:618, :1053-1054, :1091) and runs _preprocess_kpcn (:487-582) on them -- the
 // raw frame is read from disk and reduced once per count.  Here the frame is staged once at S = spp samples and
-//   wcmc_preprocess_kpcn_prefix      forms the (h, w, 44) buffer of every count s_lo..s_hi from ONE read of the raw frame;
-//   wcmc_assemble_*_patches_prefix   crop a batch at s samples out of per-sample buffers that hold S_total.
+// wcmc_preprocess_kpcn_prefix forms the (h, w, 44) buffer of every count s_lo..s_hi from ONE read of the raw frame.  (A batch at s
+// samples out of per-sample buffers that hold S_total is the patch assemblers' own `S_total, s` pair: preprocess.hip, sbmc_data.hip.)
 #include "data_step.h"
 
 namespace wcmc {
@@ -110,34 +110,4 @@ extern "C" int wcmc_preprocess_kpcn_prefix(const float* raw, int h, int w, int S
   hipLaunchKernelGGL(ms_kpcn_prefix_finish_kernel, dim3(pp_grid(npix * KP_C), (unsigned)n_counts), dim3(256), 0, st, out, ws, h, w,
                      s_lo);
   return check_launch("preprocess_kpcn_prefix(finish)");
-}
-
-extern "C" int wcmc_assemble_kpcn_patches_prefix(const float* kpcn, const float* llpm, const float* gt, const int* origins, int B,
-                                                 int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in,
-                                                 float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
-                                                 float* target_diffuse, float* target_specular, float* target_total,
-                                                 void* stream) {
-  WCMC_REQUIRE(kpcn && gt && origins && B > 0 && H > 0 && W > 0 && P > 0 && P <= H && P <= W && diffuse_in && specular_in &&
-                   diffuse_buffer && specular_buffer && albedo && target_diffuse && target_specular && target_total,
-               WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_prefix: bad argument");
-  WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_patches_prefix: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_prefix: llpm given without a paths output");
-  return pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, nullptr, B, H, W, S_total, s, P, diffuse_in, specular_in, diffuse_buffer,
-                                 specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
-                                 (hipStream_t)stream);
-}
-
-extern "C" int wcmc_assemble_sample_patches_prefix(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                                   const int* origins, int B, int H, int W, int S_total, int s, int P,
-                                                   int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
-                                                   float* target_image, void* stream) {
-  WCMC_REQUIRE(sbmc_s && gt && origins && B > 0 && H > 0 && W > 0 && P > 0 && P <= H && P <= W && radiance && features &&
-                   target_image && (!use_sbmc_buf || sbmc_p),
-               WCMC_ERR_BAD_ARG, "assemble_sample_patches_prefix: bad argument");
-  WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
-               "assemble_sample_patches_prefix: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_patches_prefix: llpm given without a paths output");
-  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, nullptr, B, H, W, S_total, s, P, use_g_buf, use_sbmc_buf, radiance, features,
-                            paths, target_image, (hipStream_t)stream);
 }

@@ -303,7 +303,7 @@ namespace wcmc {
 struct PatchOut {
   float *din, *sin, *dbuf, *sbuf, *alb, *paths, *tdif, *tspec, *ttot;
 };
-// AUG (the `_aug` entry point): output pixel (y, x) of patch b takes the window position patch_map gives for
+// AUG (a transforms table is given): output pixel (y, x) of patch b takes the window position patch_map gives for
 // the code transforms[b] -- the destination is untouched, only the source index is permuted, and a source is still one whole
 // 176-byte record plus its S * 148 bytes of llpm.  The backward differences are those of the transformed frame: taken again
 // from the stored value channels against the source of output (y, x - 1) / (y - 1, x) -- thirteen floats of one more record each,
@@ -384,54 +384,31 @@ __global__ __launch_bounds__(256) void pp_assemble_kpcn_kernel(const float* __re
   }
 }
 
-int pp_assemble_kpcn_launch(const float* kpcn, const float* llpm, const float* gt, const int* origins, const int* transforms, int B,
-                            int H, int W, int S_total, int s, int P, float* diffuse_in, float* specular_in, float* diffuse_buffer,
-                            float* specular_buffer, float* albedo, float* paths, float* target_diffuse, float* target_specular,
-                            float* target_total, hipStream_t stream) {
+}  // namespace wcmc
+
+extern "C" int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float* gt, const int* origins,
+                                          const int* transforms, int B, int H, int W, int S_total, int s, int P, float* diffuse_in,
+                                          float* specular_in, float* diffuse_buffer, float* specular_buffer, float* albedo,
+                                          float* paths, float* target_diffuse, float* target_specular, float* target_total,
+                                          void* stream) {
+  WCMC_REQUIRE(kpcn && gt && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse &&
+                   target_specular && target_total,
+               WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: null pointer");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: B, H, W, P must be positive");
+  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: a %d-pixel patch does not fit the %d x %d frame", P, H, W);
+  // (the sample counts are read with llpm alone: without it S_total = s = 0 is a plain batch)
+  WCMC_REQUIRE(!llpm || (1 <= s && s <= S_total), WCMC_ERR_BAD_ARG,
+               "assemble_kpcn_patches: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: llpm given without a paths output");
   PatchOut o{diffuse_in, specular_in, diffuse_buffer, specular_buffer, albedo, paths, target_diffuse, target_specular,
              target_total};
   const int64_t total = (int64_t)B * P * P;
   const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-  if (transforms) {
-    hipLaunchKernelGGL(pp_assemble_kpcn_kernel<true>, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, transforms, o, B, H, W,
-                       S_total, s, P);
-    return check_launch("assemble_kpcn_patches_aug");
-  }
-  hipLaunchKernelGGL(pp_assemble_kpcn_kernel<false>, dim3(grid), dim3(256), 0, stream, kpcn, llpm, gt, origins, transforms, o, B, H, W,
-                     S_total, s, P);
+  if (transforms)
+    hipLaunchKernelGGL(pp_assemble_kpcn_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, gt, origins,
+                       transforms, o, B, H, W, S_total, s, P);
+  else
+    hipLaunchKernelGGL(pp_assemble_kpcn_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, kpcn, llpm, gt, origins,
+                       transforms, o, B, H, W, S_total, s, P);
   return check_launch("assemble_kpcn_patches");
-}
-}  // namespace wcmc
-
-extern "C" int wcmc_assemble_kpcn_patches(const float* kpcn, const float* llpm, const float* gt, const int* origins,
-                                          int B, int H, int W, int S, int P, float* diffuse_in, float* specular_in,
-                                          float* diffuse_buffer, float* specular_buffer, float* albedo, float* paths,
-                                          float* target_diffuse, float* target_specular, float* target_total,
-                                          void* stream) {
-  WCMC_REQUIRE(kpcn && gt && origins && B > 0 && H > 0 && W > 0 && P > 0 && P <= H && P <= W && diffuse_in &&
-                   specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse && target_specular &&
-                   target_total && (!llpm || (paths && S > 0)),
-               WCMC_ERR_BAD_ARG, "assemble_kpcn_patches: bad argument");
-  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, nullptr, B, H, W, S, S, P, diffuse_in, specular_in, diffuse_buffer,
-                                       specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
-                                       (hipStream_t)stream);
-}
-
-extern "C" int wcmc_assemble_kpcn_patches_aug(const float* kpcn, const float* llpm, const float* gt, const int* origins,
-                                              const int* transforms, int B, int H, int W, int S_total, int s, int P,
-                                              float* diffuse_in, float* specular_in, float* diffuse_buffer, float* specular_buffer,
-                                              float* albedo, float* paths, float* target_diffuse, float* target_specular,
-                                              float* target_total, void* stream) {
-  WCMC_REQUIRE(transforms, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: null transforms (one code 0..7 per patch)");
-  WCMC_REQUIRE(kpcn && gt && origins && diffuse_in && specular_in && diffuse_buffer && specular_buffer && albedo && target_diffuse &&
-                   target_specular && target_total,
-               WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: null pointer");
-  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: B, H, W, P must be positive");
-  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: a %d-pixel patch does not fit the %d x %d frame", P, H, W);
-  WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
-               "assemble_kpcn_patches_aug: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_kpcn_patches_aug: llpm given without a paths output");
-  return wcmc::pp_assemble_kpcn_launch(kpcn, llpm, gt, origins, transforms, B, H, W, S_total, s, P, diffuse_in, specular_in,
-                                       diffuse_buffer, specular_buffer, albedo, paths, target_diffuse, target_specular, target_total,
-                                       (hipStream_t)stream);
 }

@@ -101,7 +101,7 @@ __device__ __forceinline__ float* sa_dst(const SampleBatch& a, int k, int b, int
   return a.tgt + ((int64_t)b * 3 + ch) * plane;
 }
 
-// AUG (the `_aug` entry point): the unit's 32 output pixels (y, x0 + px) take the window positions patch_map
+// AUG (a transforms table is given): the unit's 32 output pixels (y, x0 + px) take the window positions patch_map
 // gives for the code transforms[b].  The map is affine, so the 32 source runs are `step` floats apart -- one pixel pitch forwards
 // or backwards along a source row, or a whole source row up or down for the transposing codes -- instead of one pitch; every
 // channel is a copy, and the LDS tile and the writes are the plain form's.
@@ -155,46 +155,13 @@ __global__ __launch_bounds__(256) void sa_assemble_kernel(SampleBatch a, const i
   }
 }
 
-static unsigned sb_grid(int64_t work) {
-  const int64_t b = ceil_div64(work, 256);
-  return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
-int sa_assemble_launch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, const int* origins,
-                       const int* transforms, int B, int H, int W, int S_total, int s, int P, int use_g_buf, int use_sbmc_buf,
-                       float* radiance, float* features, float* paths, float* target_image, hipStream_t stream) {
-  SampleBatch a;
-  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = target_image;
-  a.ng = use_g_buf ? 24 : 3;
-  a.F = a.ng + (use_sbmc_buf ? SA_CP : 0) + (llpm ? 1 : 0);
-  a.src[0] = SampleSrc{sbmc_s, SB_S, s, S_total, 3 + a.ng, 0};
-  a.src[1] = SampleSrc{sbmc_p, SA_CP, s, S_total, use_sbmc_buf ? SA_CP : 0, 0};
-  a.src[2] = SampleSrc{llpm, SA_CL, s, S_total, llpm ? SA_CL : 0, 0};
-  a.src[3] = SampleSrc{gt, SA_CG, 1, 1, 3, 0};
-  const int64_t rows = (int64_t)B * P * ((P + SA_XT - 1) / SA_XT);
-  int64_t units = 0;
-  for (int k = 0; k < 4; ++k) {
-    a.src[k].first = units;
-    if (a.src[k].nout > 0) units += rows * ((a.src[k].S + SA_SC - 1) / SA_SC);
-  }
-  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  if (transforms) {
-    hipLaunchKernelGGL(sa_assemble_kernel<true>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins,
-                       transforms, units, B, H, W, s, P);
-    return check_launch("assemble_sample_patches_aug");
-  }
-  hipLaunchKernelGGL(sa_assemble_kernel<false>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds, stream, a, origins,
-                     transforms, units, B, H, W, s, P);
-  return check_launch("assemble_sample_patches");
-}
-
 // ------------------------------------------------------------------ sample-based tiles of the mirror-extended frame (wcmc_amd.denoise)
 // sa_assemble_kernel with other addressing: the tile's origin is in frame coordinates and may lie up to `pad` pixels outside, the
 // source row is m(r) and each of the chunk's 32 pixels has its own source column m(c + px) (ft_mirror: a chunk that straddles a
 // frame edge runs backwards on the far side of it).  All three buffers are per sample, so a mirrored position is a copy of its
 // image's record -- nothing is recomputed -- and there is no gt source.  LDS tile and write pattern as above; the reads run along c
 // too, a pixel per half-wave.
-// AUG (the `_aug` entry point): the whole launch reads the frame through one dihedral transform `code`.
+// AUG (a code t in 1..7): the whole launch reads the frame through one dihedral transform `code`.
 // Origins and mirror are those of the TRANSFORMED frame (Ht x Wt: W x H for odd codes) and frame_map gives each of the chunk's 32
 // pixels its source record: along a source row for even codes, down a source column for odd ones.  Every channel is a copy; the
 // LDS tile and the writes are unchanged.
@@ -252,71 +219,56 @@ __global__ __launch_bounds__(256) void sa_assemble_tiles_kernel(SampleBatch a, c
 
 using namespace wcmc;
 
-// the three sources and the work units of a tile launch (both entry points below)
-static SampleBatch sa_tile_batch(const float* sbmc_s, const float* sbmc_p, const float* llpm, int S, int P, int B, int use_g_buf,
-                                 int use_sbmc_buf, float* radiance, float* features, float* paths, int64_t* units_out) {
+// The sources and the work units of a launch of either assembly kernel.  The per-sample buffers hold S_total samples per pixel, the
+// outputs the first s of them; gt (patches only) is the fourth source, and without it neither its slot nor target_image is read.
+static SampleBatch sa_batch(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt, int B, int S_total, int s,
+                            int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
+                            float* target_image, int64_t* units_out) {
   SampleBatch a;
-  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = nullptr;
+  a.rad = radiance; a.feat = features; a.paths = paths; a.tgt = target_image;
   a.ng = use_g_buf ? 24 : 3;
   a.F = a.ng + (use_sbmc_buf ? SA_CP : 0) + (llpm ? 1 : 0);
-  a.src[0] = SampleSrc{sbmc_s, SB_S, S, S, 3 + a.ng, 0};
-  a.src[1] = SampleSrc{sbmc_p, SA_CP, S, S, use_sbmc_buf ? SA_CP : 0, 0};
-  a.src[2] = SampleSrc{llpm, SA_CL, S, S, llpm ? SA_CL : 0, 0};
-  a.src[3] = SampleSrc{nullptr, SA_CG, 1, 1, 0, 0};
+  a.src[0] = SampleSrc{sbmc_s, SB_S, s, S_total, 3 + a.ng, 0};
+  a.src[1] = SampleSrc{sbmc_p, SA_CP, s, S_total, use_sbmc_buf ? SA_CP : 0, 0};
+  a.src[2] = SampleSrc{llpm, SA_CL, s, S_total, llpm ? SA_CL : 0, 0};
+  a.src[3] = SampleSrc{gt, SA_CG, 1, 1, gt ? 3 : 0, 0};
   const int64_t rows = (int64_t)B * P * ((P + SA_XT - 1) / SA_XT);
   int64_t units = 0;
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < (gt ? 4 : 3); ++k) {
     a.src[k].first = units;
-    if (a.src[k].nout > 0) units += rows * ((S + SA_SC - 1) / SA_SC);
+    if (a.src[k].nout > 0) units += rows * ((a.src[k].S + SA_SC - 1) / SA_SC);
   }
   *units_out = units;
   return a;
 }
 
+constexpr size_t SA_LDS = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);   // the widest source's tile
+
 extern "C" int wcmc_assemble_sample_tiles(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
-                                          int H, int W, int S, int P, int pad, int use_g_buf, int use_sbmc_buf, float* radiance,
-                                          float* features, float* paths, void* stream) {
+                                          int H, int W, int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf,
+                                          float* radiance, float* features, float* paths, void* stream) {
+  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: the transform code must lie in 0..7 (got %d)", t);
   WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: null pointer");
   WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: use_sbmc_buf needs sbmc_p");
   WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: llpm needs a paths output");
   WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
                "assemble_sample_tiles: B, H, W, P must be positive and pad non-negative");
   WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: S must be positive (got %d)", S);
-  WCMC_REQUIRE(pad < H && pad < W, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles: pad = %d must be smaller than the %d x %d frame (one reflection)", pad, H, W);
-  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
-  WCMC_REQUIRE(P <= H + 2 * pad && P <= W + 2 * pad, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles: a %d-pixel tile does not fit the %d x %d frame extended by %d", P, H, W, pad);
-  int64_t units;
-  const SampleBatch a = sa_tile_batch(sbmc_s, sbmc_p, llpm, S, P, B, use_g_buf, use_sbmc_buf, radiance, features, paths, &units);
-  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  hipLaunchKernelGGL(sa_assemble_tiles_kernel<false>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds,
-                     (hipStream_t)stream, a, origins, units, H, W, P, 0);
-  return check_launch("assemble_sample_tiles");
-}
-
-extern "C" int wcmc_assemble_sample_tiles_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const int* origins, int B,
-                                              int H, int W, int S, int P, int pad, int t, int use_g_buf, int use_sbmc_buf,
-                                              float* radiance, float* features, float* paths, void* stream) {
-  WCMC_REQUIRE(t >= 0 && t <= 7, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: the transform code must lie in 0..7 (got %d)", t);
-  WCMC_REQUIRE(sbmc_s && origins && radiance && features, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: null pointer");
-  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: use_sbmc_buf needs sbmc_p");
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: llpm needs a paths output");
-  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0 && pad >= 0, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles_aug: B, H, W, P must be positive and pad non-negative");
-  WCMC_REQUIRE(S > 0, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: S must be positive (got %d)", S);
   const int Ht = t & 1 ? W : H, Wt = t & 1 ? H : W;
   WCMC_REQUIRE(pad < Ht && pad < Wt, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles_aug: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
-  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles_aug: a %d-pixel tile has no interior inside a pad of %d", P, pad);
+               "assemble_sample_tiles: pad = %d must be smaller than the transformed %d x %d frame (one reflection)", pad, Ht, Wt);
+  WCMC_REQUIRE(P > 2 * pad, WCMC_ERR_BAD_ARG, "assemble_sample_tiles: a %d-pixel tile has no interior inside a pad of %d", P, pad);
   WCMC_REQUIRE(P <= Ht + 2 * pad && P <= Wt + 2 * pad, WCMC_ERR_BAD_ARG,
-               "assemble_sample_tiles_aug: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
+               "assemble_sample_tiles: a %d-pixel tile does not fit the transformed %d x %d frame extended by %d", P, Ht, Wt, pad);
   int64_t units;
-  const SampleBatch a = sa_tile_batch(sbmc_s, sbmc_p, llpm, S, P, B, use_g_buf, use_sbmc_buf, radiance, features, paths, &units);
-  const size_t lds = (size_t)SA_XT * ((SA_SC * SA_CP) | 1) * sizeof(float);
-  hipLaunchKernelGGL(sa_assemble_tiles_kernel<true>, dim3((unsigned)(units > 65535 ? 65535 : units)), dim3(256), lds,
-                     (hipStream_t)stream, a, origins, units, H, W, P, t);
-  return check_launch("assemble_sample_tiles_aug");
+  const SampleBatch a = sa_batch(sbmc_s, sbmc_p, llpm, nullptr, B, S, S, P, use_g_buf, use_sbmc_buf, radiance, features, paths, nullptr,
+                                 &units);
+  const dim3 grid((unsigned)(units > 65535 ? 65535 : units));
+  if (t)
+    hipLaunchKernelGGL(sa_assemble_tiles_kernel<true>, grid, dim3(256), SA_LDS, (hipStream_t)stream, a, origins, units, H, W, P, t);
+  else
+    hipLaunchKernelGGL(sa_assemble_tiles_kernel<false>, grid, dim3(256), SA_LDS, (hipStream_t)stream, a, origins, units, H, W, P, 0);
+  return check_launch("assemble_sample_tiles");
 }
 
 extern "C" int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples, int C, int max_depth, float* out_s, float* out_p,
@@ -334,37 +286,35 @@ extern "C" int wcmc_preprocess_sbmc(const float* raw, int64_t nsamples, int C, i
     hipLaunchKernelGGL(sb_preprocess_tiled_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), lds,
                        (hipStream_t)stream, raw, out_s, out_p, nsamples, C, d);
   } else {
-    hipLaunchKernelGGL(sb_preprocess_kernel, dim3(sb_grid(nsamples * (SB_S + 11 * d))), dim3(256), 0, (hipStream_t)stream, raw,
+    hipLaunchKernelGGL(sb_preprocess_kernel, dim3(pp_grid(nsamples * (SB_S + 11 * d))), dim3(256), 0, (hipStream_t)stream, raw,
                        out_s, out_p, nsamples, C, d);
   }
   return check_launch("preprocess_sbmc");
 }
 
 extern "C" int wcmc_assemble_sample_patches(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                            const int* origins, int B, int H, int W, int S, int P, int use_g_buf,
-                                            int use_sbmc_buf, float* radiance, float* features, float* paths,
+                                            const int* origins, const int* transforms, int B, int H, int W, int S_total, int s,
+                                            int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
                                             float* target_image, void* stream) {
-  WCMC_REQUIRE(sbmc_s && gt && origins && B > 0 && H > 0 && W > 0 && S > 0 && P > 0 && P <= H && P <= W && radiance &&
-                   features && target_image && (!use_sbmc_buf || sbmc_p) && (!llpm || paths),
-               WCMC_ERR_BAD_ARG, "assemble_sample_patches: bad argument");
-  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, nullptr, B, H, W, S, S, P, use_g_buf, use_sbmc_buf, radiance, features,
-                            paths, target_image, (hipStream_t)stream);
-}
-
-extern "C" int wcmc_assemble_sample_patches_aug(const float* sbmc_s, const float* sbmc_p, const float* llpm, const float* gt,
-                                                const int* origins, const int* transforms, int B, int H, int W, int S_total, int s,
-                                                int P, int use_g_buf, int use_sbmc_buf, float* radiance, float* features, float* paths,
-                                                float* target_image, void* stream) {
-  WCMC_REQUIRE(transforms, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: null transforms (one code 0..7 per patch)");
   WCMC_REQUIRE(sbmc_s && gt && origins && radiance && features && target_image, WCMC_ERR_BAD_ARG,
-               "assemble_sample_patches_aug: null pointer");
-  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: use_sbmc_buf needs sbmc_p");
-  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: B, H, W, P must be positive");
-  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: a %d-pixel patch does not fit the %d x %d frame", P, H,
+               "assemble_sample_patches: null pointer");
+  WCMC_REQUIRE(!use_sbmc_buf || sbmc_p, WCMC_ERR_BAD_ARG, "assemble_sample_patches: use_sbmc_buf needs sbmc_p");
+  WCMC_REQUIRE(B > 0 && H > 0 && W > 0 && P > 0, WCMC_ERR_BAD_ARG, "assemble_sample_patches: B, H, W, P must be positive");
+  WCMC_REQUIRE(P <= H && P <= W, WCMC_ERR_BAD_ARG, "assemble_sample_patches: a %d-pixel patch does not fit the %d x %d frame", P, H,
                W);
   WCMC_REQUIRE(1 <= s && s <= S_total, WCMC_ERR_BAD_ARG,
-               "assemble_sample_patches_aug: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
-  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_patches_aug: llpm given without a paths output");
-  return sa_assemble_launch(sbmc_s, sbmc_p, llpm, gt, origins, transforms, B, H, W, S_total, s, P, use_g_buf, use_sbmc_buf, radiance,
-                            features, paths, target_image, (hipStream_t)stream);
+               "assemble_sample_patches: the prefix must satisfy 1 <= s <= S_total (got %d of %d)", s, S_total);
+  WCMC_REQUIRE(!llpm || paths, WCMC_ERR_BAD_ARG, "assemble_sample_patches: llpm given without a paths output");
+  int64_t units;
+  const SampleBatch a = sa_batch(sbmc_s, sbmc_p, llpm, gt, B, S_total, s, P, use_g_buf, use_sbmc_buf, radiance, features, paths,
+                                 target_image, &units);
+  const dim3 grid((unsigned)(units > 65535 ? 65535 : units));
+  if (transforms)
+    hipLaunchKernelGGL(sa_assemble_kernel<true>, grid, dim3(256), SA_LDS, (hipStream_t)stream, a, origins, transforms, units, B, H, W, s,
+                       P);
+  else
+    hipLaunchKernelGGL(sa_assemble_kernel<false>, grid, dim3(256), SA_LDS, (hipStream_t)stream, a, origins, transforms, units, B, H, W,
+                       s, P);
+  return check_launch("assemble_sample_patches");
 }
+

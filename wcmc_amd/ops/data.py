@@ -138,6 +138,12 @@ def _need_origins(who, origins):
     assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
 
 
+def _need_coords(who, coords):
+    """The (B, 6) tile table as the stitch kernels read it: a contiguous int32 device tensor."""
+    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6 and coords.is_contiguous()):
+        raise RuntimeError("%s: coords must be a contiguous device int32 (B, 6) tensor" % who)
+
+
 def check_patch_transforms(transforms, b, who="assemble_kpcn_patches"):
     """Host check of a table of patch transform codes: ``b`` int32 codes in 0..7, one per patch, as a 1-D
     tensor or array.  The codes are data, as origins are: a device tensor is read back here (which synchronises), so a caller that
@@ -158,7 +164,7 @@ def check_patch_transforms(transforms, b, who="assemble_kpcn_patches"):
 
 
 def _transforms_dev(who, transforms, b, device, check):
-    """The (b,) int32 device table the `_aug` kernels read.  ``check=False`` still refuses a wrong dtype or length (no read-back)."""
+    """The (b,) int32 device table the patch kernels read.  ``check=False`` still refuses a wrong dtype or length (no read-back)."""
     if check:
         check_patch_transforms(transforms, b, who)
     if not isinstance(transforms, torch.Tensor):
@@ -169,11 +175,24 @@ def _transforms_dev(who, transforms, b, device, check):
     return transforms.to(device).contiguous()
 
 
+def _kpcn_batch_shapes(b, s, patch, targets):
+    """Entries of a KPCN batch of ``b`` windows (patches with ``targets``, tiles without); ``s``: llpm's samples, None without llpm."""
+    cin = 34 if s is None else 35
+    shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
+              "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
+              "kpcn_albedo": (b, 3, patch, patch)}
+    if targets:
+        shapes.update({k: (b, 3, patch, patch) for k in ("target_diffuse", "target_specular", "target_total")})
+    if s is not None:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    return shapes
+
+
 def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None, transforms=None, check_transforms=True):
     """The batch dictionary of the KPCN base model for windows of `patch` pixels at `origins` ((B, 2) int32 device
-    tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device).  ``spp``: the batch takes
-    the first ``spp`` of llpm's samples (``wcmc_assemble_kpcn_patches_prefix``; ``kpcn`` is then that count's buffer); None: all.
-    ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array; ``wcmc_assemble_kpcn_patches_aug``,
+    tensor of (row, column)) of one image's preprocessed buffers (datasets.py:1026-1146 on the device;
+    ``wcmc_assemble_kpcn_patches``).  ``spp``: the batch takes the first ``spp`` of llpm's samples (``kpcn`` is then that count's
+    buffer); None: all.  ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array;
     DESIGN.md section 20): entry b is ``rot90(fliplr(w) if t & 4 else w, t & 3)`` of its window w as if the whole frame had been
     transformed before preprocessing -- per-pixel channels copied, the backward differences retaken along the new axes."""
     _need_cuda(kpcn, gt)
@@ -187,26 +206,15 @@ def assemble_kpcn_patches(kpcn, llpm, gt, origins, patch, spp=None, transforms=N
     s_total = s
     if spp is not None and llpm is not None:
         s = _check_prefix("assemble_kpcn_patches", spp, s_total)
-    cin = 35 if llpm is not None else 34
-    shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
-              "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
-              "kpcn_albedo": (b, 3, patch, patch), "target_diffuse": (b, 3, patch, patch),
-              "target_specular": (b, 3, patch, patch), "target_total": (b, 3, patch, patch)}
-    if llpm is not None:
-        shapes["paths"] = (b, s, 36, patch, patch)
-    out = _aligned_views(shapes, kpcn.device)
-    outs = (_ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]), _ptr(out["kpcn_diffuse_buffer"]),
-            _ptr(out["kpcn_specular_buffer"]), _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
-            _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream())
-    ins = (_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
-    if transforms is not None:                        # (without llpm no sample is read: the entry point still wants 1 <= s <= S_total)
-        tr = _transforms_dev("assemble_kpcn_patches", transforms, b, kpcn.device, check_transforms)
-        check(lib().wcmc_assemble_kpcn_patches_aug(*ins[:4], ctypes.c_void_p(tr.data_ptr()), b, h, w, max(s_total, 1), max(s, 1),
-                                                   patch, *outs), "assemble_kpcn_patches_aug")
-    elif spp is not None and llpm is not None:
-        check(lib().wcmc_assemble_kpcn_patches_prefix(*ins, s_total, s, patch, *outs), "assemble_kpcn_patches_prefix")
-    else:                                             # (without llpm nothing in the batch depends on the sample count)
-        check(lib().wcmc_assemble_kpcn_patches(*ins, s, patch, *outs), "assemble_kpcn_patches")
+    out = _aligned_views(_kpcn_batch_shapes(b, s if llpm is not None else None, patch, targets=True), kpcn.device)
+    tr = None if transforms is None else _transforms_dev("assemble_kpcn_patches", transforms, b, kpcn.device, check_transforms)
+    # (without llpm nothing in the batch depends on the sample counts: 0, 0)
+    check(lib().wcmc_assemble_kpcn_patches(_ptr(kpcn), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), _ptr(tr), b, h, w,
+                                           s_total, s, patch, _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
+                                           _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
+                                           _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _ptr(out["target_diffuse"]),
+                                           _ptr(out["target_specular"]), _ptr(out["target_total"]), _stream()),
+          "assemble_kpcn_patches")
     return out
 
 
@@ -255,15 +263,26 @@ def _check_sample_buffers(who, sbmc_p, llpm, h, w, s):
                              % (who, name, h, w, s, c, tuple(t.shape)))
 
 
+def _sample_batch_shapes(b, s, patch, use_g_buf, use_sbmc_buf, use_llpm_buf, target):
+    """Entries of a sample-based batch of ``b`` windows at ``s`` samples (patches with the ``target`` image, tiles without)."""
+    f = sample_feature_size(use_g_buf, use_sbmc_buf, use_llpm_buf)
+    shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
+    if use_llpm_buf:
+        shapes["paths"] = (b, s, 36, patch, patch)
+    if target:
+        shapes["target_image"] = (b, 3, patch, patch)
+    return shapes
+
+
 def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=True, use_sbmc_buf=True, check_origins=True,
                             spp=None, transforms=None):
     """The batch dictionary of the SBMC / LBMC interfaces (``radiance``, ``features``, ``paths`` as (B, S, C, P, P) and
     ``target_image``) for windows of ``patch`` pixels at ``origins`` ((B, 2) int32 (row, column); numpy or tensor) of one image's
-    buffers (datasets.py:1045-1073, 1086-1118 and ``_transpose`` on the device, one launch).  ``sbmc_p`` may be None without
-    ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  ``check_origins=False``: the caller has checked them
-    on the host (checking a device tensor here synchronises).  ``spp``: the batch takes the first ``spp`` samples of the buffers
-    (``wcmc_assemble_sample_patches_prefix``: the buffers are per-sample, so the prefix is a slice); None: all of them.
-    ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array; ``wcmc_assemble_sample_patches_aug``,
+    buffers (datasets.py:1045-1073, 1086-1118 and ``_transpose`` on the device, one launch: ``wcmc_assemble_sample_patches``).
+    ``sbmc_p`` may be None without ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.
+    ``check_origins=False``: the caller has checked them on the host (checking a device tensor here synchronises).  ``spp``: the
+    batch takes the first ``spp`` samples of the buffers (they are per-sample, so the prefix is a slice); None: all of them.
+    ``transforms``: None, or one dihedral code 0..7 per patch ((B,) int32 tensor or array;
     DESIGN.md section 20): every entry of patch b is ``rot90(fliplr(w) if t & 4 else w, t & 3)`` of its window w on the two pixel
     axes -- all channels are per sample, so all are copies (subpixel and light directions included: not re-expressed).  The table is
     checked on the host together with the origins (``check_origins``)."""
@@ -288,23 +307,13 @@ def assemble_sample_patches(sbmc_s, sbmc_p, llpm, gt, origins, patch, use_g_buf=
     s_total = s
     if spp is not None:
         s = _check_prefix("assemble_sample_patches", spp, s_total)
-    f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
-    shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
-    if llpm is not None:
-        shapes["paths"] = (b, s, 36, patch, patch)
-    shapes["target_image"] = (b, 3, patch, patch)
-    out = _aligned_views(shapes, sbmc_s.device)
-    ins = (_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt), ctypes.c_void_p(origins.data_ptr()), b, h, w)
-    outs = (patch, int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
-            _ptr(out.get("paths")), _ptr(out["target_image"]), _stream())
-    if transforms is not None:
-        tr = _transforms_dev("assemble_sample_patches", transforms, b, sbmc_s.device, check_origins)
-        check(lib().wcmc_assemble_sample_patches_aug(*ins[:5], ctypes.c_void_p(tr.data_ptr()), b, h, w, s_total, s, *outs),
-              "assemble_sample_patches_aug")
-    elif spp is not None:
-        check(lib().wcmc_assemble_sample_patches_prefix(*ins, s_total, s, *outs), "assemble_sample_patches_prefix")
-    else:
-        check(lib().wcmc_assemble_sample_patches(*ins, s, *outs), "assemble_sample_patches")
+    out = _aligned_views(_sample_batch_shapes(b, s, patch, use_g_buf, use_sbmc_buf, llpm is not None, target=True), sbmc_s.device)
+    tr = None if transforms is None else _transforms_dev("assemble_sample_patches", transforms, b, sbmc_s.device, check_origins)
+    check(lib().wcmc_assemble_sample_patches(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm), _ptr(gt),
+                                             ctypes.c_void_p(origins.data_ptr()), _ptr(tr), b, h, w, s_total, s, patch,
+                                             int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]),
+                                             _ptr(out["features"]), _ptr(out.get("paths")), _ptr(out["target_image"]), _stream()),
+          "assemble_sample_patches")
     return out
 
 
@@ -413,9 +422,7 @@ def stitch_tiles(out, p_buffers, coords, out_rad, out_path=None, patch=128):
     ``check_tile_coords``; out_rad (3, H, W) and out_path ((S, C, H, W), or a dict of them keyed like p_buffers) are written
     in place.  Bit-identical to the slice copies."""
     _need_cuda(out, out_rad)
-    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
-            and coords.is_contiguous()):
-        raise RuntimeError("stitch_tiles: coords must be a contiguous device int32 (B, 6) tensor")
+    _need_coords("stitch_tiles", coords)
     b, c3, ho, wo = out.shape
     _, h, w = out_rad.shape
     assert c3 == 3 and coords.shape[0] == b and out_rad.shape[0] == 3 and out_rad.is_contiguous()
@@ -472,7 +479,7 @@ def check_frame_transforms(codes):
 
 
 def _frame_transform(who, transform):
-    """One whole-frame code: None and 0 are the plain call path."""
+    """One whole-frame code: None is 0, the frame as it is."""
     if transform is None:
         return 0
     if isinstance(transform, bool) or not isinstance(transform, numbers.Integral) or not 0 <= int(transform) <= 7:
@@ -487,9 +494,7 @@ def stitch_tiles_aug(out, coords, out_rad, transform, accumulate, patch=128):
     the TRANSFORMED frame's table, which passed ``check_tile_coords`` against the transformed sizes.  No P-buffers."""
     _need_cuda(out, out_rad)
     t = _frame_transform("stitch_tiles_aug", transform)
-    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
-            and coords.is_contiguous()):
-        raise RuntimeError("stitch_tiles_aug: coords must be a contiguous device int32 (B, 6) tensor")
+    _need_coords("stitch_tiles_aug", coords)
     b, c3, ho, wo = out.shape
     _, h, w = out_rad.shape
     assert c3 == 3 and coords.shape[0] == b and out_rad.shape[0] == 3 and out_rad.is_contiguous() and out_rad.dtype == torch.float32
@@ -508,9 +513,7 @@ def stitch_tiles_blend(out, coords, acc, wsum, blend, transform=0, patch=128, pa
     refuses a ``blend`` above ``(patch - 2 * pad) / 2`` or one that gives weight to a replicated pixel.  No P-buffers."""
     _need_cuda(out, acc, wsum)
     t = _frame_transform("stitch_tiles_blend", transform)
-    if not (coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 6
-            and coords.is_contiguous()):
-        raise RuntimeError("stitch_tiles_blend: coords must be a contiguous device int32 (B, 6) tensor")
+    _need_coords("stitch_tiles_blend", coords)
     if isinstance(blend, bool) or not isinstance(blend, numbers.Integral):
         raise ValueError("stitch_tiles_blend: the feather half-width should be an integer, got %r" % (blend,))
     b, c3, ho, wo = out.shape
@@ -544,8 +547,8 @@ def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=Tr
     (checking a device tensor here synchronises).
 
     ``transform``: a dihedral code 1..7 assembles the tiles of the frame as if the RAW frame had been transformed by ``T_t`` before
-    preprocessing (``wcmc_assemble_kpcn_tiles_aug``): ``origins`` are then in the transformed frame's
-    coordinates and are checked against its sizes (W x H for odd codes).  0 or None takes the plain call path."""
+    preprocessing: ``origins`` are then in the transformed frame's coordinates and are checked against its
+    sizes (W x H for odd codes).  0 or None is the frame as it is."""
     _need_cuda(kpcn)
     _need_origins("assemble_kpcn_tiles", origins)
     h, w = kpcn.shape[:2]
@@ -558,21 +561,8 @@ def assemble_kpcn_tiles(kpcn, llpm, origins, patch=128, pad=32, check_origins=Tr
         _need_cuda(llpm)
         assert llpm.shape[:2] == (h, w) and llpm.shape[3] == 37 and llpm.is_contiguous()
         s = llpm.shape[2]
-    cin = 35 if llpm is not None else 34
-    shapes = {"kpcn_diffuse_in": (b, cin, patch, patch), "kpcn_specular_in": (b, cin, patch, patch),
-              "kpcn_diffuse_buffer": (b, 3, patch, patch), "kpcn_specular_buffer": (b, 3, patch, patch),
-              "kpcn_albedo": (b, 3, patch, patch)}
-    if llpm is not None:
-        shapes["paths"] = (b, s, 36, patch, patch)
-    out = _aligned_views(shapes, kpcn.device)
-    if t:
-        check(lib().wcmc_assemble_kpcn_tiles_aug(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t,
-                                                 _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
-                                                 _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
-                                                 _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _stream()),
-              "assemble_kpcn_tiles_aug")
-        return out
-    check(lib().wcmc_assemble_kpcn_tiles(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad,
+    out = _aligned_views(_kpcn_batch_shapes(b, s if llpm is not None else None, patch, targets=False), kpcn.device)
+    check(lib().wcmc_assemble_kpcn_tiles(_ptr(kpcn), _ptr(llpm), ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t,
                                          _ptr(out["kpcn_diffuse_in"]), _ptr(out["kpcn_specular_in"]),
                                          _ptr(out["kpcn_diffuse_buffer"]), _ptr(out["kpcn_specular_buffer"]),
                                          _ptr(out["kpcn_albedo"]), _ptr(out.get("paths")), _stream()), "assemble_kpcn_tiles")
@@ -617,8 +607,7 @@ def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_
     never built).  ``sbmc_p`` may be None without ``use_sbmc_buf``; ``llpm`` None leaves ``paths`` and the path weight out.  The
     origins are data and are checked on the host (``check_tile_origins``); ``check_origins=False``: the caller has checked the
     table once (checking a device tensor here synchronises).  ``transform``: as ``assemble_kpcn_tiles``'s -- a code 1..7 reads the
-    frame through ``T_t`` (``wcmc_assemble_sample_tiles_aug``), the origins being those of the transformed frame; every channel is a
-    copy."""
+    frame through ``T_t``, the origins being those of the transformed frame; every channel is a copy."""
     t = _frame_transform("assemble_sample_tiles", transform)
     _need_cuda(sbmc_s)
     _need_origins("assemble_sample_tiles", origins)
@@ -631,20 +620,9 @@ def assemble_sample_tiles(sbmc_s, sbmc_p, llpm, origins, patch=128, pad=32, use_
     if check_origins:
         check_tile_origins(origins, *((w, h) if t & 1 else (h, w)), patch, pad, who="assemble_sample_tiles")
     b = origins.shape[0]
-    f = sample_feature_size(use_g_buf, use_sbmc_buf, llpm is not None)
-    shapes = {"radiance": (b, s, 3, patch, patch), "features": (b, s, f, patch, patch)}
-    if llpm is not None:
-        shapes["paths"] = (b, s, 36, patch, patch)
-    out = _aligned_views(shapes, sbmc_s.device)
-    if t:
-        check(lib().wcmc_assemble_sample_tiles_aug(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
-                                                   ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t,
-                                                   int(bool(use_g_buf)), int(bool(use_sbmc_buf)), _ptr(out["radiance"]),
-                                                   _ptr(out["features"]), _ptr(out.get("paths")), _stream()),
-              "assemble_sample_tiles_aug")
-        return out
+    out = _aligned_views(_sample_batch_shapes(b, s, patch, use_g_buf, use_sbmc_buf, llpm is not None, target=False), sbmc_s.device)
     check(lib().wcmc_assemble_sample_tiles(_ptr(sbmc_s), _ptr(sbmc_p if use_sbmc_buf else None), _ptr(llpm),
-                                           ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, int(bool(use_g_buf)),
+                                           ctypes.c_void_p(origins.data_ptr()), b, h, w, s, patch, pad, t, int(bool(use_g_buf)),
                                            int(bool(use_sbmc_buf)), _ptr(out["radiance"]), _ptr(out["features"]),
                                            _ptr(out.get("paths")), _stream()), "assemble_sample_tiles")
     return out
