@@ -33,8 +33,9 @@
 extern "C" {
 #endif
 
-#define WCMC_ABI_VERSION 3     /* 2: `terms` of the GEMM entry points, packing mode 2 (round 3); round 4 widened the value ranges only (terms = 1, mode 3)
-                                * 3: the four batch assemblers take `transforms, S_total, s` / `t`: the _prefix and _aug names are gone */
+#define WCMC_ABI_VERSION 4     /* 2: `terms` of the GEMM entry points, packing mode 2 (round 3); round 4 widened the value ranges only (terms = 1, mode 3)
+                                * 3: the four batch assemblers take `transforms, S_total, s` / `t`: the _prefix and _aug names are gone
+                                * 4: the fused PathNet chains take `x_split, x_nchw, strides` / `h_hi` / `out, h_hi`: the _nchw, _save and _saved names are gone */
 
 enum wcmc_status {
   WCMC_OK = 0,
@@ -233,64 +234,55 @@ int wcmc_embed3_fwd(const void* x_split, int64_t M, int Cin, const void* wp0, co
                     const float* b1, const void* wp2, const float* b2, float* y, void* stream);
 /* The same forward with the spp mean of y leaving in the same launch (support/networks.py:35-36: y.view(B, S, ...).mean(1)):
  * y_mean fp32 [M / S][64], the sums formed s ascending in fp32 and multiplied by 1 / S -- bit-identical to wcmc_spp_reduce on
- * the stored y, which is then not read again.  M = B * S * HW with HW % 64 == 0 (wcmc_embed3_mean_supported). */
+ * the stored y, which is then not read again.  M = B * S * HW with HW % 64 == 0 (wcmc_embed3_mean_supported).
+ * wcmc_embed3_mean_fwd and wcmc_embed3_bwd take x in one of two forms; EXACTLY ONE of x_split / x_nchw is non-null (both, or
+ * neither: WCMC_ERR_BAD_ARG, before anything else):
+ *   x_split  the split tensor, as in wcmc_embed3_fwd; the two strides are ignored.
+ *   x_nchw   x WHERE IT LIES: fp32, channel-first -- N = M / HW samples of Cin channel planes of HW floats, sample / channel
+ *            stride x_sample_stride / x_channel_stride floats (a slice of a larger buffer in N and C is fine), each H x W plane
+ *            contiguous -- instead of its split copy (`paths` arrives channel-first, support/networks.py:31-33, and this chain is
+ *            its only reader: the split copy was a pass over memory of its own).  The kernels load a tile's Cin rows of 64 pixels
+ *            and split them with wcmc_split_from_nchw's arithmetic on the way into the LDS tile, so y, y_mean and the six gradients
+ *            equal those of the x_split form BIT FOR BIT.  wcmc_embed3_nchw_supported (host only, no device needed): Cin <= 64,
+ *            H * W % 64 == 0 (a 64-pixel tile lies in one sample), sw == 1 and sh == W (a contiguous plane), sc >= H * W; anything
+ *            else takes the split copy.  x_nchw needs 4-byte alignment only. */
 int wcmc_embed3_mean_supported(int S, int64_t HW);
-int wcmc_embed3_mean_fwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                         const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
-                         void* stream);
-int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                    const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride,
-                    const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0,
-                    float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes, void* stream);
-/* The same two launches reading x WHERE IT LIES: fp32, channel-first -- N = M / HW samples of Cin channel planes of HW floats,
- * sample / channel stride x_sample_stride / x_channel_stride floats (a slice of a larger buffer in N and C is fine), each H x W
- * plane contiguous -- instead of its split copy (`paths` arrives channel-first, support/networks.py:31-33, and this chain is its
- * only reader: the split copy was a pass over memory of its own).  The kernels load a tile's Cin rows of 64 pixels and split them
- * with wcmc_split_from_nchw's arithmetic on the way into the LDS tile, so y, y_mean and the six gradients equal those of the
- * x_split entries BIT FOR BIT.  wcmc_embed3_nchw_supported (host only, no device needed): Cin <= 64, H * W % 64 == 0 (a 64-pixel
- * tile lies in one sample), sw == 1 and sh == W (a contiguous plane), sc >= H * W; anything else takes the split copy.  x needs
- * 4-byte alignment only. */
 int wcmc_embed3_nchw_supported(int Cin, int64_t N, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw);
-int wcmc_embed3_mean_fwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin,
-                              const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
-                              const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream);
-int wcmc_embed3_bwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin, const void* wp0,
-                         const float* b0, const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy,
-                         int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0,
-                         float* db0, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
-                         void* stream);
+int wcmc_embed3_mean_fwd(const void* x_split, const float* x_nchw, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M,
+                         int Cin, const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
+                         const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream);
+int wcmc_embed3_bwd(const void* x_split, const float* x_nchw, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M,
+                    int Cin, const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wt1,
+                    const void* wt2, const float* gy, int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S,
+                    int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
+                    void* workspace, size_t workspace_bytes, void* stream);
 /* ---------------------------------------------------------------- PathNet.final, fused (support/networks.py:39-42)
  * out = ConvChain(128 -> 128 -> outc <= 8, ksize 1, ReLU, ReLU)(cat([y, repeat_S(prop)], 1)): y fp32 over M = B*S*HW pixels
  * (64 channels, pixel stride y_pixel_stride floats), prop fp32 over B*HW pixels (64 channels), out / gout fp32 [M][os] with
  * os = 4 for outc <= 4, else 8 (an NHWC view of outc channels; round 4: up to eight, the reference's --pnet_out_size 6 runs,
- * train_kpcn.py:209-212); HW % 64 == 0.  Neither the concatenation nor the hidden activation is written: the backward recomputes
- * them, writes dy [M][64] and dprop [B*HW][64] (the sum over the S samples) and the weight / bias gradients (OIHW, ks = 1) in the
- * default mode's arithmetic.  Forward bit-identical to wcmc_cat_broadcast_split + wcmc_conv1x1_pair_bf16x3.
- *   wp0 / wp1  forward packs (mode 0) of the two layers, wt0 / wt1 their data-gradient packs (mode 1). */
+ * train_kpcn.py:209-212); HW % 64 == 0.  The concatenation is never written.  The backward writes dy [M][64] and dprop [B*HW][64]
+ * (the sum over the S samples) and the weight / bias gradients (OIHW, ks = 1) in the default mode's arithmetic.  Forward
+ * bit-identical to wcmc_cat_broadcast_split + wcmc_conv1x1_pair_bf16x3.
+ *   wp0 / wp1  forward packs (mode 0) of the two layers, wt0 / wt1 their data-gradient packs (mode 1).
+ * All the backward uses of the hidden activation is its bf16 hi plane (ReLU gate, one-term dW1), all it uses of out is its sign.
+ * It either recomputes both or reads them from the forward:
+ *   wcmc_final2_fwd  h_hi null: nothing but out is written.  h_hi non-null: also writes h_hi, a dense bf16 plane [M][128] (256 B
+ *                    per pixel); out is bit for bit the same.
+ *   wcmc_final2_bwd  out and h_hi both null: recomputes the hidden activation and out from y and prop.  Both non-null: reads that
+ *                    h_hi, and out as the forward wrote it (read only): no recomputation (58 instead of 118 MFMAs per 64-pixel
+ *                    tile and wave), all eight results bit for bit the same.  Exactly one of them null: WCMC_ERR_BAD_ARG.
+ * Errors before any launch, after those of the other arguments: out without h_hi or h_hi without out in the backward
+ * WCMC_ERR_BAD_ARG, an h_hi / out that is not 16-byte aligned WCMC_ERR_ALIGNMENT (the output of the forward, null or misaligned:
+ * WCMC_ERR_BAD_ARG), then a short workspace WCMC_ERR_WORKSPACE (wcmc_final2_bwd_workspace_bytes() serves both forms). */
 int wcmc_final2_supported(int C1, int C2, int Chid, int outc, int64_t HW);
 size_t wcmc_final2_bwd_workspace_bytes(void);
 int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                    const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* stream);
+                    const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
+                    void* stream);
 int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
                     const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                    const void* wt1, const float* gout, float* dy, float* dprop, float* dw0, float* db0, float* dw1,
-                    float* db1, void* workspace, size_t workspace_bytes, void* stream);
-/* The same pair with h's hi plane and out handed from the forward to the backward instead of recomputed.  All the backward uses
- * of the hidden activation is its bf16 hi plane (ReLU gate, one-term dW1), all it uses of out is its sign:
- *   wcmc_final2_fwd_save   wcmc_final2_fwd that also writes h_hi, a dense bf16 plane [M][128] (256 B per pixel); out is bit for
- *                          bit wcmc_final2_fwd's.
- *   wcmc_final2_bwd_saved  wcmc_final2_bwd on that h_hi and on out as the forward wrote it (read only): no recomputation (58
- *                          instead of 118 MFMAs per 64-pixel tile and wave), all eight results bit for bit wcmc_final2_bwd's.
- * Errors before any launch, after those of wcmc_final2_fwd / _bwd's own arguments: a null h_hi / out WCMC_ERR_BAD_ARG, one
- * that is not 16-byte aligned WCMC_ERR_ALIGNMENT (the output of the forward: WCMC_ERR_BAD_ARG, as in wcmc_final2_fwd), then a
- * short workspace WCMC_ERR_WORKSPACE (wcmc_final2_bwd_workspace_bytes() serves both backwards). */
-int wcmc_final2_fwd_save(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                         const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
-                         void* stream);
-int wcmc_final2_bwd_saved(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                          const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                          const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
-                          float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream);
+                    const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
+                    float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream);
 size_t wcmc_conv2d_igemm_colsum_elems(int N, int Ho, int Wo, int Cout);
 int wcmc_colsum_finish(const float* partial, int N, int Ho, int Wo, int Cout, float* db, void* stream);
 /* Which kernel a launch WOULD run, from the code that launches, without touching the device (no GPU needed).  Each writes two

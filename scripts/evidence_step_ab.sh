@@ -6,10 +6,6 @@ echo "# two-stream captured step, U-Net 3x3 kernel of round 6 off / on (debug li
 python3 scripts/ab_step_switch.py ENV:WCMC_HALO3 3 2>/dev/null | grep -v FeatureMSE
 echo "# the same with the halves in series on one stream"
 AB_SERIAL=1 python3 scripts/ab_step_switch.py ENV:WCMC_HALO3 2 2>/dev/null | grep -v FeatureMSE
-echo "# wave-private final-chain forward, 16 pixels per wave (100 VGPRs) against the shipped kernel"
-python3 scripts/ab_step_switch.py ENV:WCMC_F2W=0,1 2 2>/dev/null | grep -v FeatureMSE
-echo "# ... 32 pixels per wave (192 VGPRs)"
-python3 scripts/ab_step_switch.py ENV:WCMC_F2W=0,2 2 2>/dev/null | grep -v FeatureMSE
 echo "# clock and power while the step replays; all-zero parameters against the drawn ones"
 python3 scripts/probe_power.py 2>/dev/null | grep -v FeatureMSE
 if [ -d _r05 ]; then

@@ -1,11 +1,14 @@
-"""The in-place entries of the fused PathNet.embedding (``wcmc_embed3_*_nchw``): what can be checked without a GPU."""
+"""The in-place form of the fused PathNet.embedding (the ``x_nchw`` source of ``wcmc_embed3_mean_fwd`` / ``wcmc_embed3_bwd``): what
+can be checked without a GPU."""
 import os
 import re
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("wcmc_embed3_nchw_supported", "wcmc_embed3_mean_fwd_nchw", "wcmc_embed3_bwd_nchw")
+NEW = ("wcmc_embed3_nchw_supported", "wcmc_embed3_mean_fwd", "wcmc_embed3_bwd")
+# ABI 4 folded the in-place spellings (and the final chain's _save / _saved ones) into the base names: these four are gone
+GONE = ("wcmc_embed3_mean_fwd_nchw", "wcmc_embed3_bwd_nchw", "wcmc_final2_fwd_save", "wcmc_final2_bwd_saved")
 
 
 def _lib():
@@ -56,25 +59,36 @@ def test_entries_reject_bad_arguments_before_any_launch():
     a = (ctypes.addressof(buf) + 15) // 16 * 16
     P = ctypes.c_void_p
     w = [P(a)] * 8
-    # H * W = 60: not readable in place; null x; misaligned x
-    assert h.wcmc_embed3_mean_fwd_nchw(P(a), 36 * 60, 60, 120, 36, *w, 1, 60, None) < 0
-    assert b"wcmc_embed3_nchw_supported" in h.wcmc_last_error()
-    assert h.wcmc_embed3_mean_fwd_nchw(None, 36 * 64, 64, 128, 36, *w, 1, 64, None) < 0
-    assert h.wcmc_embed3_mean_fwd_nchw(P(a + 2), 36 * 64, 64, 128, 36, *w, 1, 64, None) < 0
+    BAD_ARG, ALIGNMENT = -1, -2
+    err = lambda: h.wcmc_last_error().decode()
+    # H * W = 60: not readable in place; neither source; both sources; misaligned x_nchw
+    assert h.wcmc_embed3_mean_fwd(None, P(a), 36 * 60, 60, 120, 36, *w, 1, 60, None) == BAD_ARG
+    assert "wcmc_embed3_nchw_supported" in err()
+    assert h.wcmc_embed3_mean_fwd(None, None, 36 * 64, 64, 128, 36, *w, 1, 64, None) == BAD_ARG and "neither" in err()
+    assert h.wcmc_embed3_mean_fwd(P(a), P(a), 36 * 64, 64, 128, 36, *w, 1, 64, None) == BAD_ARG and "both" in err()
+    assert h.wcmc_embed3_mean_fwd(None, P(a + 2), 36 * 64, 64, 128, 36, *w, 1, 64, None) == ALIGNMENT
     g = [P(a)] * 7
-    assert h.wcmc_embed3_bwd_nchw(None, 36 * 64, 64, 128, 36, *g, 64, P(a), 64, 1, 64, 1.0, *([P(a)] * 6), P(a), 1 << 30, None) < 0
-    assert h.wcmc_embed3_bwd_nchw(P(a), 36 * 64, 63, 128, 36, *g, 64, P(a), 64, 1, 64, 1.0, *([P(a)] * 6), P(a), 1 << 30, None) < 0
+    tail = (64, P(a), 64, 1, 64, 1.0, *([P(a)] * 6), P(a), 1 << 30, None)
+    assert h.wcmc_embed3_bwd(None, None, 36 * 64, 64, 128, 36, *g, *tail) == BAD_ARG and "neither" in err()
+    assert h.wcmc_embed3_bwd(P(a), P(a), 36 * 64, 64, 128, 36, *g, *tail) == BAD_ARG and "both" in err()
+    assert h.wcmc_embed3_bwd(None, P(a), 36 * 64, 63, 128, 36, *g, *tail) == BAD_ARG                   # channel planes overlap
+    assert "wcmc_embed3_nchw_supported" in err()
 
 
 def test_header_binding_and_integration_notes_list_the_entries():
-    from wcmc_amd._lib import SIGNATURES
+    from wcmc_amd._lib import SIGNATURES, I, L, P
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wcmc_hip.h")).read(), flags=re.S)
     notes = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in NEW:
         m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, header, flags=re.S)
         assert m and name in SIGNATURES and name in notes, name
         assert len(m.group(1).split(",")) == len(SIGNATURES[name][1]), name
-    # the in-place entries take (x, sample stride, channel stride) where the split entries take x_split
-    for new, old in (("wcmc_embed3_mean_fwd_nchw", "wcmc_embed3_mean_fwd"), ("wcmc_embed3_bwd_nchw", "wcmc_embed3_bwd")):
-        assert len(SIGNATURES[new][1]) == len(SIGNATURES[old][1]) + 2 and SIGNATURES[new][1][3:] == SIGNATURES[old][1][1:]
+        if name != NEW[0]:      # both sources lead: (x_split, x_nchw, sample stride, channel stride, M, Cin, ...)
+            lead = [p.strip() for p in m.group(1).split(",")[:6]]
+            assert [p.rsplit(None, 1)[-1].lstrip("*") for p in lead] == ["x_split", "x_nchw", "x_sample_stride", "x_channel_stride", "M", "Cin"]
+            assert SIGNATURES[name][1][:6] == [P, P, L, L, L, I], name
+    # the plain forward keeps the split source alone: the merged entries take three arguments more in its place
+    assert len(SIGNATURES["wcmc_embed3_mean_fwd"][1]) == len(SIGNATURES["wcmc_embed3_fwd"][1]) + 3 + 3
+    for name in GONE:
+        assert name not in SIGNATURES and not re.search(r"\b%s\b" % name, header), name
     assert "EMBED_IN_PLACE" in notes

@@ -41,7 +41,7 @@ def test_library_exports_every_declared_symbol():
     h = lib()
     for name in declared:
         assert getattr(h, name) is not None
-    assert h.wcmc_abi_version() == 3
+    assert h.wcmc_abi_version() == 4
     # pure host-side size queries work without a GPU
     assert h.wcmc_conv2d_packed_elems(100, 100, 5) == 112 * 2528
     assert h.wcmc_conv2d_packed_elems(441, 100, 5) == 448 * 2528

@@ -104,7 +104,7 @@ def test_abi_declares_the_prefix_entry_points_and_rejects_bad_counts():
     import ctypes
     from wcmc_amd import _lib
     L = _lib.lib()
-    assert L.wcmc_abi_version() == 3
+    assert L.wcmc_abi_version() == 4
     null, one = ctypes.c_void_p(0), ctypes.c_void_p(16)
     assert L.wcmc_preprocess_kpcn_prefix_workspace_bytes(10, 7, 3) == 3 * (2 * 70 + 4) * 4
     assert L.wcmc_preprocess_kpcn_prefix_workspace_bytes(10, 7, 0) == 0

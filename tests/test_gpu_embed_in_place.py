@@ -1,5 +1,5 @@
-"""The fused PathNet.embedding reading the channel-first ``paths`` where it lies (``wcmc_embed3_mean_fwd_nchw`` / ``wcmc_embed3_bwd_nchw``,
-``ops.embed_in_place``) against the same fused chain on the split copy (``ops.presplit_shared``): y, its spp mean and the six parameter
+"""The fused PathNet.embedding reading the channel-first ``paths`` where it lies (the ``x_nchw`` source of ``wcmc_embed3_mean_fwd`` /
+``wcmc_embed3_bwd``, ``ops.embed_in_place``) against the same fused chain on the split copy (``ops.presplit_shared``): y, its spp mean and the six parameter
 gradients BIT FOR BIT -- the in-place kernels split with the split pass's arithmetic into the very LDS tile the GEMMs read, and
 everything behind that tile is the same code."""
 import pytest

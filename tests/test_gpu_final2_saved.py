@@ -1,5 +1,5 @@
-"""PathNet.final's backward on the forward's saved tensors (``wcmc_final2_fwd_save`` / ``wcmc_final2_bwd_saved``,
-``ops.SAVE_FINAL_HIDDEN``) against the backward that recomputes them (``wcmc_final2_bwd``).
+"""PathNet.final's backward on the forward's saved tensors (``wcmc_final2_fwd`` with ``h_hi``, ``wcmc_final2_bwd`` with ``out`` and
+``h_hi``; ``ops.SAVE_FINAL_HIDDEN``) against the backward that recomputes them (the same entries with null pointers there).
 
 The saved route changes no arithmetic: every MFMA that remains runs on the same operands in the same order on the same grid, so
 every comparison here is ``torch.equal`` -- there is no tolerance to choose.
@@ -35,14 +35,19 @@ def inputs(case):
 
 
 class _Spy:
-    """The library, with the names of the entries called through it."""
+    """The library, with the names and the arguments of the entries called through it."""
 
     def __init__(self, real):
         self.real, self.calls = real, []
 
     def __getattr__(self, name):
-        self.calls.append(name)
-        return getattr(self.real, name)
+        fn = getattr(self.real, name)
+
+        def recorded(*args):
+            self.calls.append((name, args))
+            return fn(*args)
+
+        return recorded
 
 
 def run_routes(case, flat, prop, params, g, monkeypatch):
@@ -62,8 +67,13 @@ def run_routes(case, flat, prop, params, g, monkeypatch):
         out = o.cat_broadcast_chain(fd, pd, s, 1, 0, ["relu", "relu"], ps)
         out.backward(g.to(DEV))
         res[save] = (out.detach().clone(), [fd.grad.clone(), pd.grad.clone()] + [t.grad.clone() for t in ps])
-        called = [c for c in spy.calls if c.startswith("wcmc_final2_fwd") or (c.startswith("wcmc_final2_bwd") and "workspace" not in c)]
-        assert called == (["wcmc_final2_fwd_save", "wcmc_final2_bwd_saved"] if save else ["wcmc_final2_fwd", "wcmc_final2_bwd"]), called
+        called = [c for c in spy.calls if c[0].startswith("wcmc_final2_fwd") or (c[0].startswith("wcmc_final2_bwd") and "workspace" not in c[0])]
+        assert [c[0] for c in called] == ["wcmc_final2_fwd", "wcmc_final2_bwd"], called
+        # the form each launch took: (h_hi) of the forward, (out, h_hi) of the backward -- filled on the saved route, null on the other
+        given = [bool(a.value) for a in (called[0][1][13], called[1][1][15], called[1][1][16])]
+        assert given == [save] * 3, (save, given)
+        if save:            # ... and the backward was handed the forward's own output and plane
+            assert called[1][1][15].value == called[0][1][12].value and called[1][1][16].value == called[0][1][13].value
     return res
 
 
@@ -111,7 +121,7 @@ def test_saved_route_gates_dead_units_like_the_recompute_route(dead, monkeypatch
 
 
 def _fwd_pair(o, case, flat, prop, params):
-    """(out of wcmc_final2_fwd, out and plane of wcmc_final2_fwd_save), called through the C ABI on the same inputs."""
+    """(out of wcmc_final2_fwd without h_hi, out and plane of it with h_hi), called through the C ABI on the same inputs."""
     from wcmc_amd._lib import check, lib
     b, s, h, w, outc = case
     fd, pd = o.to_nhwc_raw(flat.to(DEV)), o.to_nhwc_raw(prop.to(DEV))
@@ -125,8 +135,8 @@ def _fwd_pair(o, case, flat, prop, params):
     out0 = torch.full((m, osz), 7.0, device=DEV)
     out1 = torch.full((m, osz), 9.0, device=DEV)
     plane = torch.full((m, 128), 3.0, device=DEV, dtype=torch.bfloat16)
-    check(lib().wcmc_final2_fwd(*args(out0), stream), "final2_fwd")
-    check(lib().wcmc_final2_fwd_save(*args(out1), plane.data_ptr(), stream), "final2_fwd_save")
+    check(lib().wcmc_final2_fwd(*args(out0), None, stream), "final2_fwd")
+    check(lib().wcmc_final2_fwd(*args(out1), plane.data_ptr(), stream), "final2_fwd with h_hi")
     torch.cuda.synchronize()
     return out0, out1, plane
 
@@ -134,12 +144,12 @@ def _fwd_pair(o, case, flat, prop, params):
 @gpu
 @pytest.mark.parametrize("case", [(2, 3, 8, 8, 3), (1, 2, 8, 24, 8), (5, 2, 64, 64, 3)])
 def test_saved_plane_is_the_hi_plane_of_the_hidden_activation(case, monkeypatch):
-    """The plane ``wcmc_final2_fwd_save`` writes = the hi plane of the layer-by-layer path's hidden activation, bit for bit, taken
+    """The plane ``wcmc_final2_fwd`` writes into ``h_hi`` = the hi plane of the layer-by-layer path's hidden activation, bit for bit, taken
     two ways: from the split tensor that path wrote (``wcmc_conv1x1_pair_bf16x3``'s first result), and from its ``DEBUG_ACTS``
     value (hi + lo, exact in fp32) run through the library's own split (``wcmc_split_bf16``).  The second way cannot tell the hi
     plane where hi + lo lies exactly half way between two bf16 values (lo was itself rounded, to half an ulp of hi: the re-split
     then rounds to even, which need not be hi): there the plane must be one of those two neighbours, everywhere else the re-split's
-    hi, and the first way pins every entry.  ``out`` of ``_save`` = ``wcmc_final2_fwd``'s, bit for bit."""
+    hi, and the first way pins every entry.  ``out`` with ``h_hi`` = ``out`` without it, bit for bit."""
     o = ops()
     b, s, h, w, outc = case
     m = b * s * h * w
@@ -182,27 +192,32 @@ def test_saved_plane_is_the_hi_plane_of_the_hidden_activation(case, monkeypatch)
 
 # ---------------------------------------------------------------------------------------------- host side: no GPU needed
 def test_new_entries_refuse_bad_arguments_before_any_launch():
-    """Null / misaligned ``h_hi`` and ``out`` and a short workspace: the error codes include/wcmc_hip.h documents, from checks
-    that precede every HIP call (so this runs without a device; a launch would not return one of these codes)."""
+    """Misaligned ``h_hi`` and ``out``, one of the pair without the other in the backward, and a short workspace: the error codes
+    include/wcmc_hip.h documents, from checks that precede every HIP call (so this runs without a device; a launch would not return
+    one of these codes).  (A null ``h_hi`` in the forward, and a null pair in the backward, are the plain forms: no refusals.)"""
     from wcmc_amd._lib import lib
     L = lib()
     BAD_ARG, ALIGNMENT, WORKSPACE = -1, -2, -3
     null, one, odd = ctypes.c_void_p(0), ctypes.c_void_p(16), ctypes.c_void_p(24)      # never dereferenced by the checks
     nb = L.wcmc_final2_bwd_workspace_bytes()
     common = (one, 64, one, 64, 1, 1, 64, one, one, one, one, 3)
-    fwd = lambda out, h: L.wcmc_final2_fwd_save(*common, out, h, null)
-    bwd = lambda out, h, n=nb: L.wcmc_final2_bwd_saved(*common, one, one, one, out, h, one, one, one, one, one, one, one, n, null)
-    for rc, want, what in ((fwd(one, null), BAD_ARG, "fwd_save: null h_hi"), (fwd(one, odd), ALIGNMENT, "fwd_save: misaligned h_hi"),
-                           (fwd(null, one), BAD_ARG, "fwd_save: null out"), (fwd(odd, one), BAD_ARG, "fwd_save: misaligned out"),
-                           (bwd(null, one), BAD_ARG, "bwd_saved: null out"), (bwd(one, null), BAD_ARG, "bwd_saved: null h_hi"),
-                           (bwd(odd, one), ALIGNMENT, "bwd_saved: misaligned out"), (bwd(one, odd), ALIGNMENT, "bwd_saved: misaligned h_hi"),
-                           (bwd(one, one, nb - 1), WORKSPACE, "bwd_saved: short workspace"),
-                           (bwd(one, one, 0), WORKSPACE, "bwd_saved: no workspace bytes")):
-        assert rc == want, (what, rc, L.wcmc_last_error().decode())
-    fwd(one, null)
-    assert "final2" in L.wcmc_last_error().decode()
+    fwd = lambda out, h: L.wcmc_final2_fwd(*common, out, h, null)
+    bwd = lambda out, h, n=nb: L.wcmc_final2_bwd(*common, one, one, one, out, h, one, one, one, one, one, one, one, n, null)
+    for call, want, what in ((lambda: fwd(one, odd), ALIGNMENT, "fwd: misaligned h_hi"),
+                             (lambda: fwd(null, one), BAD_ARG, "fwd: null out"), (lambda: fwd(odd, one), BAD_ARG, "fwd: misaligned out"),
+                             (lambda: fwd(null, null), BAD_ARG, "fwd, plain form: null out"),
+                             (lambda: bwd(one, null), BAD_ARG, "bwd: out without h_hi"), (lambda: bwd(null, one), BAD_ARG, "bwd: h_hi without out"),
+                             (lambda: bwd(odd, one), ALIGNMENT, "bwd: misaligned out"), (lambda: bwd(one, odd), ALIGNMENT, "bwd: misaligned h_hi"),
+                             (lambda: bwd(one, one, nb - 1), WORKSPACE, "bwd: short workspace"),
+                             (lambda: bwd(one, one, 0), WORKSPACE, "bwd: no workspace bytes"),
+                             (lambda: bwd(null, null, nb - 1), WORKSPACE, "bwd, recomputing form: short workspace")):
+        rc = call()
+        msg = L.wcmc_last_error().decode()
+        assert rc == want and "final2" in msg, (what, rc, msg)
+        if "without" in what:           # the message says which of the pair is missing
+            assert what.split(": ")[1] in msg, (what, msg)
     # a plane of 2 GiB or more does not fit the 32-bit buffer range: refused like dy
-    assert L.wcmc_final2_fwd_save(one, 64, one, 64, 1, 1, 1 << 23, one, one, one, one, 3, one, one, null) == BAD_ARG
+    assert L.wcmc_final2_fwd(one, 64, one, 64, 1, 1, 1 << 23, one, one, one, one, 3, one, one, null) == BAD_ARG
 
 
 def test_header_binding_and_libraries_agree_on_the_new_entries():
@@ -214,13 +229,18 @@ def test_header_binding_and_libraries_agree_on_the_new_entries():
         t = param.strip().rsplit(None, 1)[0] if "*" not in param else "ptr"
         return {"ptr": _lib.P, "int": _lib.I, "int64_t": _lib.L, "size_t": _lib.Z}[t]
 
-    for name, older in (("wcmc_final2_fwd_save", "wcmc_final2_fwd"), ("wcmc_final2_bwd_saved", "wcmc_final2_bwd")):
+    libs = [ctypes.CDLL(path) for path in (_lib.LIB_PATH, os.path.join(os.path.dirname(_lib.LIB_PATH), "libwcmc_hip_debug.so"))]
+    # (the pointers of the saved form: h_hi behind out in the forward; out, h_hi behind gout in the backward)
+    for name, at, names in (("wcmc_final2_fwd", 12, ["out", "h_hi", "stream"]), ("wcmc_final2_bwd", 14, ["gout", "out", "h_hi", "dy"])):
         m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, header, flags=re.S)
         assert m, name
         res, args = _lib.SIGNATURES[name]
-        assert res is _lib.I and [code(a) for a in m.group(1).split(",")] == args, name
-        assert len(args) == len(_lib.SIGNATURES[older][1]) + (1 if name.endswith("save") else 2)
-        for path in (_lib.LIB_PATH, os.path.join(os.path.dirname(_lib.LIB_PATH), "libwcmc_hip_debug.so")):
-            assert getattr(ctypes.CDLL(path), name) is not None, (path, name)
+        params = m.group(1).split(",")
+        assert res is _lib.I and [code(a) for a in params] == args, name
+        assert [p.strip().rsplit(None, 1)[-1].lstrip("*") for p in params[at:at + len(names)]] == names, name
+        for h in libs:
+            assert getattr(h, name) is not None, name
+    for gone in ("wcmc_final2_fwd_save", "wcmc_final2_bwd_saved"):
+        assert gone not in _lib.SIGNATURES and not re.search(r"\b%s\b" % gone, header) and not any(hasattr(h, gone) for h in libs), gone
     from wcmc_amd import ops
     assert ops.SAVE_FINAL_HIDDEN in (True, False) and not hasattr(ops.pathnet_fused, "SAVE_FINAL_HIDDEN")

@@ -90,19 +90,15 @@ SIGNATURES = {
     "wcmc_step_counter_advance": (I, [P, P]),
     "wcmc_final2_supported": (I, [I, I, I, I, L]),
     "wcmc_final2_bwd_workspace_bytes": (Z, []),
-    "wcmc_final2_fwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P]),
-    "wcmc_final2_bwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, Z, P]),
-    "wcmc_final2_fwd_save": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P]),
-    "wcmc_final2_bwd_saved": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, Z, P]),
+    "wcmc_final2_fwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P]),
+    "wcmc_final2_bwd": (I, [P, I, P, I, I, I, L, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, Z, P]),
     "wcmc_embed3_supported": (I, [I, I, I, I]),
     "wcmc_embed3_bwd_workspace_bytes": (Z, []),
     "wcmc_embed3_fwd": (I, [P, L, I, P, P, P, P, P, P, P, P]),
     "wcmc_embed3_mean_supported": (I, [I, L]),
-    "wcmc_embed3_mean_fwd": (I, [P, L, I, P, P, P, P, P, P, P, P, I, L, P]),
-    "wcmc_embed3_bwd": (I, [P, L, I, P, P, P, P, P, P, P, I, P, I, I, L, F, P, P, P, P, P, P, P, Z, P]),
     "wcmc_embed3_nchw_supported": (I, [I, L, L, L, L, L, L, L]),
-    "wcmc_embed3_mean_fwd_nchw": (I, [P, L, L, L, I, P, P, P, P, P, P, P, P, I, L, P]),
-    "wcmc_embed3_bwd_nchw": (I, [P, L, L, L, I, P, P, P, P, P, P, P, I, P, I, I, L, F, P, P, P, P, P, P, P, Z, P]),
+    "wcmc_embed3_mean_fwd": (I, [P, P, L, L, L, I, P, P, P, P, P, P, P, P, I, L, P]),
+    "wcmc_embed3_bwd": (I, [P, P, L, L, L, I, P, P, P, P, P, P, P, I, P, I, I, L, F, P, P, P, P, P, P, P, Z, P]),
     "wcmc_image_loss2_fwd": (I, [I, P, L, L, L, L, P, L, L, L, L, F, P, P, Z, I, I, I, I, P]),
     "wcmc_image_loss2_bwd": (I, [I, P, L, L, L, L, P, L, L, L, L, F, P, P, I, I, I, I, P]),
     "wcmc_grad_norm_clip_workspace_bytes": (Z, [I, P]),
@@ -162,7 +158,7 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
-        if h.wcmc_abi_version() != 3:
+        if h.wcmc_abi_version() != 4:
             raise RuntimeError("wcmc_amd: ABI version mismatch in %s" % LIB_PATH)
         _lib = h
     return _lib

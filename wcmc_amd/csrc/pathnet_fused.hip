@@ -528,8 +528,8 @@ __global__ __launch_bounds__(256) void embed3_bwd_finish_kernel(const float* __r
 // gradient (537 MB fp32) only to slice it into d_y and sum the other half over the samples.  Here a workgroup (eight
 // waves, one cout tile of the 128 each) owns "super-tiles": 64 pixels of one image x its S samples.  prop's 64 pixels
 // are split into the tile once per super-tile; per sample the y tile arrives, the concatenation and the hidden
-// activation live in LDS only; the backward recomputes them (wcmc_final2_bwd) or reads what it needs of them -- h's hi plane, out's
-// sign -- from a forward that wrote them (wcmc_final2_fwd_save / _bwd_saved: f2_bwd_saved below), gates with them, writes d_y, keeps
+// activation live in LDS only; the backward recomputes them (wcmc_final2_bwd without out / h_hi) or reads what it needs of them --
+// h's hi plane, out's sign -- from a forward that wrote them (wcmc_final2_fwd / _bwd with h_hi: f2_bwd_saved below), gates with them, writes d_y, keeps
 // d_prop in registers over the S samples (written once) and accumulates all weight / bias gradients in registers across the
 // workgroup's tiles.
 constexpr int F2_C = 128;                  // concatenation and hidden width
@@ -711,6 +711,83 @@ __device__ __forceinline__ void f2_bwd_partials(float* ws, float* redb, const f3
   }
 }
 
+// ---- The five stages both backwards run (f2_chain<true>, f2_bwd_saved), one copy each.  The barriers between them stay in the callers.
+// d_o = d_out . [gate > 0] of pixel px, channels 4 q ..: hi plane into its tile, exact sums (the output layer's bias gradient) on the
+// side.  gate: the four floats of out as bits, recomputed or as the forward stored them
+__device__ __forceinline__ void f2_bwd_gate(const u32x4 gate, const u32x4 go, float (&sb1)[4], u16* DOH, int px, int q) {
+  u16 hi[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float d = e3_u2f(gate[e]) > 0.f ? e3_u2f(go[e]) : 0.f;
+    sb1[e] += d;
+    hi[e] = e3_bf(d);
+  }
+  *reinterpret_cast<u32x2*>(DOH + px * F2_ORS + 4 * q) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+}
+// dh = (W1^T d_o) . [h > 0]: this wave's hidden-channel tile, k = the 32-wide step whose channels >= os are zero
+__device__ __forceinline__ void f2_bwd_dh(const u16* DOH, const u16* HH, u16* DHH, const bf16x8 t1h, const bf16x8 t1l, float (&sb0)[4], int wave,
+                                          int fr, int q) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bf16x8 dof = *reinterpret_cast<const bf16x8*>(DOH + (16 * i + fr) * F2_ORS + q * 8);
+    f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1l, dof, a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1h, dof, a, 0, 0, 0);
+    const int o = (16 * i + fr) * F2_RS + 16 * wave + 4 * q;
+    const u32x2 hm = *reinterpret_cast<const u32x2*>(HH + o);
+    u16 hi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const u16 hv = (u16)((e < 2 ? hm[0] : hm[1]) >> (16 * (e & 1)));
+      const float d = e3_f(hv) > 0.f ? a[e] : 0.f;
+      sb0[e] += d;
+      hi[e] = e3_bf(d);
+    }
+    *reinterpret_cast<u32x2*>(DHH + o) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
+  }
+}
+// dc = W0^T dh: waves 0..3 hold d_y (concat channels 0..63, into the staging tile), waves 4..7 the d_prop contribution of this sample;
+// then the weight gradients (hi x hi, pixels on k): dW0[co tile = wave][ci tile j] += dh^T c;  dW1[16][ci tile = wave] += d_o^T h
+__device__ __forceinline__ void f2_bwd_dc_dw(const F2W& t0, const u16* DHH, const u16* CH, const u16* HH, const u16* DOH, float* stg,
+                                             f32x4 (&dpacc)[4], f32x4 (&gw0)[8], f32x4& gw1, int wave, int lane, int fr, int q) {
+  f32x4 acc[4];
+  f2_gemm<2, 4>(acc, t0, DHH, nullptr, 0, fr, q);
+  if (wave < 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<float4*>(stg + (16 * i + fr) * 68 + 16 * wave + 4 * q) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dpacc[i] += acc[i];
+  }
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const bf16x8 a0 = f2_tr(DHH, F2_RS, kk, wave, lane);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gw0[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, f2_tr(CH, F2_RS, kk, j, lane), gw0[j], 0, 0, 0);
+    gw1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2_tr(DOH, F2_ORS, kk, 0, lane), f2_tr(HH, F2_RS, kk, wave, lane), gw1, 0, 0, 0);
+  }
+}
+// the d_y tile [64][68] of the sample at pixel m0 leaves as whole 256-byte rows
+__device__ __forceinline__ void f2_store_dy(const float* stg, const __amdgpu_buffer_rsrc_t dyr, int64_t m0, int tid) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = tid + 512 * k, px = v >> 4, c4 = (v & 15) * 4;
+    const float4 o = *reinterpret_cast<const float4*>(stg + px * 68 + c4);
+    const u32x4 o4 = {__builtin_bit_cast(unsigned, o.x), __builtin_bit_cast(unsigned, o.y), __builtin_bit_cast(unsigned, o.z),
+                      __builtin_bit_cast(unsigned, o.w)};
+    __builtin_amdgcn_raw_buffer_store_b128(o4, dyr, (unsigned)(m0 * 256) + (unsigned)(px * 256 + c4 * 4), 0, 0);
+  }
+}
+// d_prop of the super-tile at pixel pix0 of prop (waves 4..7): the sum over its S samples
+__device__ __forceinline__ void f2_store_dprop(const f32x4 (&dpacc)[4], const __amdgpu_buffer_rsrc_t dpr, int64_t pix0, int wave, int fr, int q) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u32x4 o4 = {e3_f2u(dpacc[i][0]), e3_f2u(dpacc[i][1]), e3_f2u(dpacc[i][2]), e3_f2u(dpacc[i][3])};
+    __builtin_amdgcn_raw_buffer_store_b128(o4, dpr, (unsigned)(pix0 * 256) + (unsigned)((16 * i + fr) * 256 + (16 * (wave - 4) + 4 * q) * 4), 0, 0);
+  }
+}
+
 // The chain as the forward computes it.  BWD: the backward that RECOMPUTES c's lo plane, h and out from y and prop (60 of its 118
 // MFMAs per tile and wave); f2_bwd_saved below reads h's hi plane and out from the forward instead.
 template <bool BWD>
@@ -792,10 +869,7 @@ __device__ __forceinline__ void f2_chain(const F2Params& p) {
           a2[0] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            // (standard k-slot order: final2w_fwd_kernel's output layer sums the same 128 products per output in another slot
-            // order, so the out recomputed here can differ from the forward's in the last ulp -- its SIGN, which is all that is
-            // used, differs for outputs within an ulp of zero only; reading the tiles in the forward's order costs this kernel
-            // eight more LDS instructions per tile and 16 % of its time: measured, not kept)
+            // (the forward's k-slot order; reading the tiles in another order cost this kernel 16 % of its time: measured, not kept)
             const int o = (16 * wave + fr) * F2_RS + c * 32 + q * 8;
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(HH + o), al = *reinterpret_cast<const bf16x8*>(HL + o);
             const bf16x8 wh = *reinterpret_cast<const bf16x8*>(W1S + fr * F2_W1RS + c * 32 + q * 8);
@@ -819,78 +893,19 @@ __device__ __forceinline__ void f2_chain(const F2Params& p) {
         __syncthreads();                                         // h is consumed: the next sample may overwrite the tiles
         continue;
       }
-      // ---- backward.  d_o = d_out . [out > 0] (hi plane into its tile; exact sums = the output layer's bias gradient), by the
-      // lanes that hold out (no second phase, no gate bits through LDS)
-      if (wave < 4 && q < oq) {
-        const int px = 16 * wave + fr;
-        u16 hi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = ov[e] > 0.f ? e3_u2f(go[e]) : 0.f;
-          sb1[e] += d;
-          hi[e] = e3_bf(d);
-        }
-        *reinterpret_cast<u32x2*>(DOH + px * F2_ORS + 4 * q) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-      }
+      // ---- backward (the shared stages; five barriers per sample with the two above).  The gate by the lanes that hold out: no
+      // second phase, no gate bits through LDS
+      if (wave < 4 && q < oq) f2_bwd_gate(u32x4{e3_f2u(ov[0]), e3_f2u(ov[1]), e3_f2u(ov[2]), e3_f2u(ov[3])}, go, sb1, DOH, 16 * wave + fr, q);
       __syncthreads();
-      // ---- dh = (W1^T d_o) . [h > 0]: this wave's hidden-channel tile, k = the 32-wide step whose channels >= 4 are zero
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16x8 dof = *reinterpret_cast<const bf16x8*>(DOH + (16 * i + fr) * F2_ORS + q * 8);
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1l, dof, a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1h, dof, a, 0, 0, 0);
-        const int o = (16 * i + fr) * F2_RS + 16 * wave + 4 * q;
-        const u32x2 hm = *reinterpret_cast<const u32x2*>(HH + o);
-        u16 hi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const u16 hv = (u16)((e < 2 ? hm[0] : hm[1]) >> (16 * (e & 1)));
-          const float d = e3_f(hv) > 0.f ? a[e] : 0.f;
-          sb0[e] += d;
-          hi[e] = e3_bf(d);
-        }
-        *reinterpret_cast<u32x2*>(DHH + o) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-      }
+      f2_bwd_dh(DOH, HH, DHH, t1h, t1l, sb0, wave, fr, q);
       __syncthreads();
-      // ---- dc = W0^T dh: waves 0..3 hold d_y (concat channels 0..63), waves 4..7 the d_prop contribution of this sample
-      f2_gemm<2, 4>(acc, t0, DHH, nullptr, 0, fr, q);
-      if (wave < 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<float4*>(stg + (16 * i + fr) * 68 + 16 * wave + 4 * q) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dpacc[i] += acc[i];
-      }
-      // ---- weight gradients (hi x hi, pixels on k): dW0[co tile = wave][ci tile j] += dh^T c;  dW1[16][ci tile = wave] += d_o^T h
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const bf16x8 a0 = f2_tr(DHH, F2_RS, kk, wave, lane);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gw0[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, f2_tr(CH, F2_RS, kk, j, lane), gw0[j], 0, 0, 0);
-        gw1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2_tr(DOH, F2_ORS, kk, 0, lane), f2_tr(HH, F2_RS, kk, wave, lane), gw1, 0, 0, 0);
-      }
+      f2_bwd_dc_dw(t0, DHH, CH, HH, DOH, stg, dpacc, gw0, gw1, wave, lane, fr, q);
       __syncthreads();
-      // d_y tile: whole 256-byte rows
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int v = tid + 512 * k, px = v >> 4, c4 = (v & 15) * 4;
-        const float4 o = *reinterpret_cast<const float4*>(stg + px * 68 + c4);
-        const u32x4 o4 = {__builtin_bit_cast(unsigned, o.x), __builtin_bit_cast(unsigned, o.y), __builtin_bit_cast(unsigned, o.z),
-                          __builtin_bit_cast(unsigned, o.w)};
-        __builtin_amdgcn_raw_buffer_store_b128(o4, dyr, (unsigned)(m0 * 256) + (unsigned)(px * 256 + c4 * 4), 0, 0);
-      }
+      f2_store_dy(stg, dyr, m0, tid);
       // (no barrier here: the next sample's y tile goes into c's planes, which nobody reads any more, and the barrier behind
       // it orders these reads of the staging tile before h's lo plane is written again)
     }
-    if (BWD && wave >= 4) {                                      // d_prop of the super-tile: the sum over its S samples
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 o4 = {e3_f2u(dpacc[i][0]), e3_f2u(dpacc[i][1]), e3_f2u(dpacc[i][2]), e3_f2u(dpacc[i][3])};
-        __builtin_amdgcn_raw_buffer_store_b128(o4, dpr, (unsigned)((b * p.HW + hw0) * 256) + (unsigned)((16 * i + fr) * 256 + (16 * (wave - 4) + 4 * q) * 4), 0, 0);
-      }
-    }
+    if (BWD && wave >= 4) f2_store_dprop(dpacc, dpr, b * p.HW + hw0, wave, fr, q);
   }
   if (BWD) f2_bwd_partials(p.ws + (int64_t)blockIdx.x * F2_WS_PER_BLOCK, red, gw0, gw1, sb0, sb1, tid);
 }
@@ -898,11 +913,11 @@ __device__ __forceinline__ void f2_chain(const F2Params& p) {
 // ------------------------------------------------------------------ PathNet.final backward on the forward's saved tensors
 // What f2_chain<true> uses of the tensors it rebuilds: of out its sign, of h its hi plane (the ReLU gate and the one-term dW1), of
 // c its hi plane (the one-term dW0).  The forward has all three: out is its result, and h's hi plane can leave its LDS tile as
-// one bf16 plane (256 B per pixel: wcmc_final2_fwd_save).  This backward loads them instead of multiplying for them -- 58 MFMAs
+// one bf16 plane (256 B per pixel: wcmc_final2_fwd with h_hi).  This backward loads them instead of multiplying for them -- 58 MFMAs
 // per 64-pixel tile and wave instead of 118, no W0 fragments, no W1 pack, no lo plane, three barriers per sample instead of
-// five -- and runs every MFMA that remains on the same operands in the same order on the same grid, so the eight results are
-// BIT-IDENTICAL to f2_chain<true>'s.  (The forward's out = relu(..) is the value f2_chain<true> recomputes, same MFMA sequence, so
-// [stored out > 0] is its gate; the debug build's wave-private forward, whose out can differ in the last ulp, writes no plane.)
+// five.  Every MFMA that remains is the same code as f2_chain<true>'s -- the five shared stages above (f2_bwd_gate .. f2_store_dprop),
+// called on the same operands in the same order on the same grid -- so the eight results are BIT-IDENTICAL to f2_chain<true>'s.
+// (The forward's out = relu(..) is the value f2_chain<true> recomputes, same MFMA sequence, so [stored out > 0] is its gate.)
 __device__ __forceinline__ void f2_bwd_saved(const F2Params& p) {
   extern __shared__ __attribute__((aligned(16))) u16 lds[];
   u16* const CH = lds; u16* const HH = lds + F2_TILE;            // c and h, hi planes
@@ -954,17 +969,8 @@ __device__ __forceinline__ void f2_bwd_saved(const F2Params& p) {
     for (int s = 0; s < p.S; ++s, m0 += p.HW) {
       f2_store64_hi(yp, CH, 0, tid);
       f2_store_h(hp, HH, tid);
-      // ---- d_o = d_out . [out > 0] (hi plane into its tile; exact sums = the output layer's bias gradient): registers only
-      if (od) {
-        u16 hi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = e3_u2f(so[e]) > 0.f ? e3_u2f(go[e]) : 0.f;
-          sb1[e] += d;
-          hi[e] = e3_bf(d);
-        }
-        *reinterpret_cast<u32x2*>(DOH + (16 * wave + fr) * F2_ORS + 4 * q) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-      }
+      // ---- the shared stages, three barriers per sample.  The gate from registers only: the stored out
+      if (od) f2_bwd_gate(so, go, sb1, DOH, 16 * wave + fr, q);
       if (s + 1 < p.S) {
         const int64_t m1 = m0 + p.HW;
         yp = f2_load64(yr, m1, p.y_ps, tid);
@@ -975,65 +981,15 @@ __device__ __forceinline__ void f2_bwd_saved(const F2Params& p) {
         }
       }
       __syncthreads();
-      // ---- dh = (W1^T d_o) . [h > 0]: this wave's hidden-channel tile, k = the 32-wide step whose channels >= os are zero
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16x8 dof = *reinterpret_cast<const bf16x8*>(DOH + (16 * i + fr) * F2_ORS + q * 8);
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1l, dof, a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(t1h, dof, a, 0, 0, 0);
-        const int o = (16 * i + fr) * F2_RS + 16 * wave + 4 * q;
-        const u32x2 hm = *reinterpret_cast<const u32x2*>(HH + o);
-        u16 hi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const u16 hv = (u16)((e < 2 ? hm[0] : hm[1]) >> (16 * (e & 1)));
-          const float d = e3_f(hv) > 0.f ? a[e] : 0.f;
-          sb0[e] += d;
-          hi[e] = e3_bf(d);
-        }
-        *reinterpret_cast<u32x2*>(DHH + o) = u32x2{(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-      }
+      f2_bwd_dh(DOH, HH, DHH, t1h, t1l, sb0, wave, fr, q);
       __syncthreads();
-      // ---- dc = W0^T dh: waves 0..3 hold d_y (concat channels 0..63), waves 4..7 the d_prop contribution of this sample
-      f32x4 acc[4];
-      f2_gemm<2, 4>(acc, t0, DHH, nullptr, 0, fr, q);
-      if (wave < 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<float4*>(stg + (16 * i + fr) * 68 + 16 * wave + 4 * q) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dpacc[i] += acc[i];
-      }
-      // ---- weight gradients (hi x hi, pixels on k): dW0[co tile = wave][ci tile j] += dh^T c;  dW1[16][ci tile = wave] += d_o^T h
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const bf16x8 a0 = f2_tr(DHH, F2_RS, kk, wave, lane);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gw0[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, f2_tr(CH, F2_RS, kk, j, lane), gw0[j], 0, 0, 0);
-        gw1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2_tr(DOH, F2_ORS, kk, 0, lane), f2_tr(HH, F2_RS, kk, wave, lane), gw1, 0, 0, 0);
-      }
+      f2_bwd_dc_dw(t0, DHH, CH, HH, DOH, stg, dpacc, gw0, gw1, wave, lane, fr, q);
       __syncthreads();
-      // d_y tile: whole 256-byte rows
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int v = tid + 512 * k, px = v >> 4, c4 = (v & 15) * 4;
-        const float4 o = *reinterpret_cast<const float4*>(stg + px * 68 + c4);
-        const u32x4 o4 = {__builtin_bit_cast(unsigned, o.x), __builtin_bit_cast(unsigned, o.y), __builtin_bit_cast(unsigned, o.z),
-                          __builtin_bit_cast(unsigned, o.w)};
-        __builtin_amdgcn_raw_buffer_store_b128(o4, dyr, (unsigned)(m0 * 256) + (unsigned)(px * 256 + c4 * 4), 0, 0);
-      }
+      f2_store_dy(stg, dyr, m0, tid);
       // (no barrier here: the next sample's c, h and d_o go into tiles nobody reads any more -- their readers sit before the
       // barrier above -- and two barriers stand between these reads of the staging tile and its next writes)
     }
-    if (wave >= 4) {                                             // d_prop of the super-tile: the sum over its S samples
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 o4 = {e3_f2u(dpacc[i][0]), e3_f2u(dpacc[i][1]), e3_f2u(dpacc[i][2]), e3_f2u(dpacc[i][3])};
-        __builtin_amdgcn_raw_buffer_store_b128(o4, dpr, (unsigned)((b * p.HW + hw0) * 256) + (unsigned)((16 * i + fr) * 256 + (16 * (wave - 4) + 4 * q) * 4), 0, 0);
-      }
-    }
+    if (wave >= 4) f2_store_dprop(dpacc, dpr, b * p.HW + hw0, wave, fr, q);
   }
   f2_bwd_partials(p.ws + (int64_t)blockIdx.x * F2_WS_PER_BLOCK, red, gw0, gw1, sb0, sb1, tid);
 }
@@ -1070,170 +1026,6 @@ __global__ __launch_bounds__(256) void final2_bwd_finish_kernel(const float* __r
   }
 }
 
-// ------------------------------------------------------------------ PathNet.final forward, wave-private (round 6)
-// final2_kernel<false> gives every wave one cout tile of a 64-pixel tile: the concatenation and the hidden activation cross the
-// workgroup through LDS behind three barriers per tile and sample, the eight waves run in lock step (all multiply, then all
-// convert), and the launch sits at 0.31 of the HBM roofline with the matrix pipe a third busy -- although its 103 GFLOP of issued
-// MFMA work (49 us) and its 319 MB (40 us at 8 TB/s) are the same order.  Here a wave owns 32 PIXELS end to end and nothing
-// but the weights is shared:
-//   * the concatenation never exists: lane (pixel n, k-group g) loads its 8 consecutive channels of y / prop straight from global
-//     memory as the MFMA's B fragment (32 contiguous bytes; the four k-groups of a pixel cover whole 128-byte lines) and splits
-//     them in registers; prop's fragments are made once per pixel tile and reused by the S samples;
-//   * W0 (hi | lo rows, 66 KB) sits in LDS for the life of the workgroup and is read as A fragments;
-//   * h = relu(W0 c + b0) goes from the accumulators into the NEXT GEMM's B fragments without leaving the lane: accumulator
-//     tile j of lane (n, q) holds hidden channels 16 j + 4 q .. + 3 of pixel n, so k-step s of the output layer takes tiles 2 s
-//     and 2 s + 1 and labels its 32 k-slots "slot (g, e) = channel 32 s + 16 (e >> 2) + 4 g + (e & 3)" -- W1's A fragments are
-//     read from LDS in that order (two 8-byte reads per plane and k-step), the same pattern the transposing reads of the
-//     weight gradients use.  No barrier in the loop, no staging tile, every wave at its own pace.
-// h is bit-identical to the layer-by-layer path (same MFMA sequence per accumulator); the output layer sums the same 128
-// products per output in another slot order.
-constexpr int F2W_RS = 2 * F2_C + 8;       // LDS row stride (u16) of a weight pack row: hi | lo | pad, rows spread over the banks
-
-__device__ __forceinline__ void f2w_split8(const u32x4 a, const u32x4 b, bf16x8& hi, bf16x8& lo) {
-  typedef __bf16 xb2 __attribute__((ext_vector_type(2)));
-  typedef float xf2 __attribute__((ext_vector_type(2)));
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const unsigned u0 = d < 2 ? a[2 * d] : b[2 * d - 4], u1 = d < 2 ? a[2 * d + 1] : b[2 * d - 3];
-    const xf2 v = {e3_u2f(u0), e3_u2f(u1)};
-    h[d] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, xb2));
-    const xf2 back = {e3_u2f(h[d] << 16), e3_u2f(h[d] & 0xffff0000u)};
-    l[d] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - back, xb2));
-  }
-  hi = __builtin_bit_cast(bf16x8, u32x4{h[0], h[1], h[2], h[3]});
-  lo = __builtin_bit_cast(bf16x8, u32x4{l[0], l[1], l[2], l[3]});
-}
-
-template <int NI>
-__global__ __launch_bounds__(512, NI == 1 ? 4 : 2) void final2w_fwd_kernel(F2Params p) {
-  extern __shared__ __attribute__((aligned(16))) u16 lds[];
-  u16* const W0S = lds;                                          // [128][F2W_RS]
-  u16* const W1S = lds + F2_C * F2W_RS;                          // [16][F2W_RS]
-  float* const B0S = reinterpret_cast<float*>(W1S + 16 * F2W_RS);      // [128]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, q = lane >> 4;
-  for (int v = tid; v < F2_C * 32; v += 512)                     // 128 rows x 32 vectors of 8 u16 (hi 16 | lo 16)
-    *reinterpret_cast<u32x4*>(W0S + (v >> 5) * F2W_RS + (v & 31) * 8) = *reinterpret_cast<const u32x4*>(p.wp0 + (int64_t)v * 8);
-  *reinterpret_cast<u32x4*>(W1S + (tid >> 5) * F2W_RS + (tid & 31) * 8) = *reinterpret_cast<const u32x4*>(p.wp1 + tid * 8);
-  if (tid < F2_C) B0S[tid] = p.b0[tid];
-  __syncthreads();
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)p.y_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)p.prop, 0, (int)p.p_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)p.o_bytes, 0x00020000);
-  float b1[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) b1[e] = (4 * q + e < p.outc) ? p.b1[4 * q + e] : 0.f;
-  const int oq = p.os >> 2;
-  const int64_t tpi = p.HW / (16 * NI), nunits = (int64_t)p.B * tpi;    // units: 16 NI pixels of one image x its S samples
-  const int nwaves = (int)gridDim.x * 8;
-  // this lane's 32 bytes of pixel (16 i + fr) and k-step cs of a 64-channel fp32 row: two 16-byte loads
-  auto load8 = [&](const __amdgpu_buffer_rsrc_t r, unsigned base, int ps, int i, int cs, u32x4& a, u32x4& b) {
-    const unsigned off = base + (unsigned)(((16 * i + fr) * ps + 32 * cs + 8 * q) * 4);
-    a = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    b = __builtin_amdgcn_raw_buffer_load_b128(r, off + 16, 0, 0);
-  };
-  for (int64_t u = (int64_t)blockIdx.x * 8 + wave; u < nunits; u += nwaves) {
-    const int64_t b = u / tpi, hw0 = (u - b * tpi) * (16 * NI);
-    bf16x8 ph[NI][2], pl[NI][2];                                   // prop's fragments: [pixel tile][k-step]
-    {
-      const unsigned base = (unsigned)((b * p.HW + hw0) * p.p_ps * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int cs = 0; cs < 2; ++cs) {
-          u32x4 a, c;
-          load8(pr, base, p.p_ps, i, cs, a, c);
-          f2w_split8(a, c, ph[i][cs], pl[i][cs]);
-        }
-    }
-    u32x4 ya[NI][2], yb[NI][2];                                    // raw y of the sample about to be multiplied
-    {
-      const unsigned base = (unsigned)(((b * p.S) * p.HW + hw0) * p.y_ps * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int cs = 0; cs < 2; ++cs) load8(yr, base, p.y_ps, i, cs, ya[i][cs], yb[i][cs]);
-    }
-    for (int s = 0; s < p.S; ++s) {
-      const int64_t m0 = (b * p.S + s) * p.HW + hw0;
-      bf16x8 yh[NI][2], yl[NI][2];
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int cs = 0; cs < 2; ++cs) f2w_split8(ya[i][cs], yb[i][cs], yh[i][cs], yl[i][cs]);
-      if (s + 1 < p.S) {                                         // the next sample's y flies under the GEMMs
-        const unsigned base = (unsigned)((m0 + p.HW) * p.y_ps * 4);
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int cs = 0; cs < 2; ++cs) load8(yr, base, p.y_ps, i, cs, ya[i][cs], yb[i][cs]);
-      }
-      // ---- h = relu(W0 c + b0), two cout tiles at a time = one k-step of the output layer; out accumulates behind them
-      f32x4 a2[NI];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) a2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // (opaque per sample: the weight fragments are loop-invariant LDS reads -- hoisted out of the sample loop they are 576 registers)
-      int wrow = fr * F2W_RS + q * 8;
-      asm volatile("" : "+v"(wrow));
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2) {
-        f32x4 acc[2][NI];
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-          const int j = 2 * s2 + jj;
-          #pragma unroll
-          for (int i = 0; i < NI; ++i) acc[jj][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const u16* wa = W0S + wrow + 16 * j * F2W_RS + c * 32;
-            const bf16x8 wh = *reinterpret_cast<const bf16x8*>(wa), wl = *reinterpret_cast<const bf16x8*>(wa + F2_C);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-              const bf16x8 ah = c < 2 ? yh[i][c & 1] : ph[i][c & 1], al = c < 2 ? yl[i][c & 1] : pl[i][c & 1];
-              acc[jj][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, ah, acc[jj][i], 0, 0, 0);
-              acc[jj][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, al, acc[jj][i], 0, 0, 0);
-              acc[jj][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, ah, acc[jj][i], 0, 0, 0);
-            }
-          }
-        }
-        // the output layer's k-step s2: slots (q, 0..3) <- tile 2 s2, slots (q, 4..7) <- tile 2 s2 + 1 of this lane
-        const f32x4 bA = *reinterpret_cast<const f32x4*>(B0S + 32 * s2 + 4 * q), bB = *reinterpret_cast<const f32x4*>(B0S + 32 * s2 + 16 + 4 * q);
-        const u16* w1a = W1S + wrow - 4 * q + 32 * s2;                // (fr F2W_RS + 4 q)
-        const u32x2 h0 = *reinterpret_cast<const u32x2*>(w1a), h1 = *reinterpret_cast<const u32x2*>(w1a + 16);
-        const u32x2 l0 = *reinterpret_cast<const u32x2*>(w1a + F2_C), l1 = *reinterpret_cast<const u32x2*>(w1a + F2_C + 16);
-        const bf16x8 w1h = __builtin_bit_cast(bf16x8, u32x4{h0[0], h0[1], h1[0], h1[1]});
-        const bf16x8 w1l = __builtin_bit_cast(bf16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          u32x4 ra, rb;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float tA = acc[0][i][e] + bA[e], tB = acc[1][i][e] + bB[e];
-            ra[e] = e3_f2u(tA > 0.f ? tA : 0.f);
-            rb[e] = e3_f2u(tB > 0.f ? tB : 0.f);
-          }
-          bf16x8 hh, hl;
-          f2w_split8(ra, rb, hh, hl);
-          a2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1l, hh, a2[i], 0, 0, 0);
-          a2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1h, hl, a2[i], 0, 0, 0);
-          a2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1h, hh, a2[i], 0, 0, 0);
-        }
-      }
-      // ---- out = relu(W1 h + b1): lanes q < oq hold (and store) output channels 4 q .. 4 q + 3 of pixel 16 i + fr
-      if (q < oq) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          u32x4 o4;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { const float t = a2[i][e] + b1[e]; o4[e] = e3_f2u((4 * q + e < p.outc && t > 0.f) ? t : 0.f); }
-          __builtin_amdgcn_raw_buffer_store_b128(o4, orr, (unsigned)(m0 * p.os * 4) + (unsigned)((16 * i + fr) * p.os * 4 + q * 16), 0, 0);
-        }
-      }
-    }
-  }
-}
-constexpr size_t F2W_LDS_FWD = (size_t)(F2_C + 16) * F2W_RS * sizeof(u16) + (size_t)F2_C * sizeof(float);
-
 static int f2_grid() { return 256; }
 constexpr size_t F2_LDS_FWD = (size_t)4 * F2_TILE * sizeof(u16);
 constexpr size_t F2_LDS_BWD = (size_t)5 * F2_TILE * sizeof(u16) + (size_t)E3_TP * F2_ORS * sizeof(u16) + (size_t)(16 * F2_C + 64 * 8) * sizeof(float) +
@@ -1254,7 +1046,7 @@ extern "C" int wcmc_embed3_supported(int Cin, int C1, int C2, int C3) {
 
 extern "C" size_t wcmc_embed3_bwd_workspace_bytes(void) { return (size_t)e3_grid_bwd() * E3_WS_PER_BLOCK * sizeof(float); }
 
-// The channel-first fp32 source the *_nchw entries read in place: N samples of Cin channel planes of H x W floats.
+// The channel-first fp32 source (x_nchw) that wcmc_embed3_mean_fwd / _bwd read in place: N samples of Cin channel planes of H x W floats.
 extern "C" int wcmc_embed3_nchw_supported(int Cin, int64_t N, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
   if (!(Cin >= 1 && Cin <= 64 && N > 0 && H > 0 && W > 0 && H <= 0x7fffffff / W)) return 0;
   const int64_t HW = H * W;
@@ -1264,10 +1056,12 @@ extern "C" int wcmc_embed3_nchw_supported(int Cin, int64_t N, int64_t H, int64_t
          (N == 1 || sn >= 0) && N <= (0x7ff00000ll >> 8) / HW;
 }
 
-// (x_nchw != null: the source of the *_nchw entries -- sample / channel stride sn / sc in floats, HW pixels per plane -- else x_split)
+// (exactly one source: x_nchw, read in place -- sample / channel stride sn / sc in floats, HW pixels per plane -- or x_split)
 static int e3_fill(E3Params& p, const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
                    const float* b1, const float* x_nchw = nullptr, int64_t sn = 0, int64_t sc = 0, int64_t HW = 0) {
-  WCMC_REQUIRE((x_split || x_nchw) && wp0 && wp1 && b0 && b1 && M > 0 && Cin >= 1 && Cin <= 64, WCMC_ERR_BAD_ARG, "embed3: bad argument");
+  WCMC_REQUIRE(!(x_split && x_nchw), WCMC_ERR_BAD_ARG, "embed3: both x_split and x_nchw given (exactly one source)");
+  WCMC_REQUIRE(x_split || x_nchw, WCMC_ERR_BAD_ARG, "embed3: neither x_split nor x_nchw given (exactly one source)");
+  WCMC_REQUIRE(wp0 && wp1 && b0 && b1 && M > 0 && Cin >= 1 && Cin <= 64, WCMC_ERR_BAD_ARG, "embed3: bad argument");
   WCMC_REQUIRE((x_nchw || aligned16(x_split)) && aligned16(wp0) && aligned16(wp1), WCMC_ERR_ALIGNMENT, "embed3: buffers must be 16-byte aligned");
   p.M = M; p.Cp0 = round_up(Cin, 8); p.Kt0 = round_up(p.Cp0, 32);
   p.wp0 = (const u16*)wp0; p.wp1 = (const u16*)wp1; p.b0 = b0; p.b1 = b1;
@@ -1301,11 +1095,11 @@ extern "C" int wcmc_embed3_fwd(const void* x_split, int64_t M, int Cin, const vo
 
 extern "C" int wcmc_embed3_mean_supported(int S, int64_t HW) { return S >= 1 && HW > 0 && HW % E3_TP == 0; }
 
-static int e3_mean_fwd(const void* x_split, const float* x_nchw, int64_t sn, int64_t sc, int64_t M, int Cin, const void* wp0, const float* b0,
-                       const void* wp1, const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
-                       void* stream) {
+extern "C" int wcmc_embed3_mean_fwd(const void* x_split, const float* x_nchw, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M,
+                                    int Cin, const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
+                                    const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream) {
   E3Params p = {};
-  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, sn, sc, HW)) return rc;
+  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, x_sample_stride, x_channel_stride, HW)) return rc;
   WCMC_REQUIRE(wp2 && b2 && y && y_mean && aligned16(wp2) && aligned16(y) && aligned16(y_mean), WCMC_ERR_BAD_ARG, "embed3_mean_fwd: bad argument");
   WCMC_REQUIRE(wcmc_embed3_mean_supported(S, HW) && M % ((int64_t)S * HW) == 0, WCMC_ERR_BAD_ARG,
                "embed3_mean_fwd: M must be B * S * HW with HW a multiple of 64 (ask wcmc_embed3_mean_supported)");
@@ -1318,26 +1112,13 @@ static int e3_mean_fwd(const void* x_split, const float* x_nchw, int64_t sn, int
   return check_launch("embed3_mean_fwd");
 }
 
-extern "C" int wcmc_embed3_mean_fwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                                    const float* b1, const void* wp2, const float* b2, float* y, float* y_mean, int S, int64_t HW,
-                                    void* stream) {
-  WCMC_REQUIRE(x_split, WCMC_ERR_BAD_ARG, "embed3: bad argument");
-  return e3_mean_fwd(x_split, nullptr, 0, 0, M, Cin, wp0, b0, wp1, b1, wp2, b2, y, y_mean, S, HW, stream);
-}
-
-extern "C" int wcmc_embed3_mean_fwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin,
-                                         const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wp2,
-                                         const float* b2, float* y, float* y_mean, int S, int64_t HW, void* stream) {
-  WCMC_REQUIRE(x, WCMC_ERR_BAD_ARG, "embed3: bad argument");
-  return e3_mean_fwd(nullptr, x, x_sample_stride, x_channel_stride, M, Cin, wp0, b0, wp1, b1, wp2, b2, y, y_mean, S, HW, stream);
-}
-
-static int e3_bwd(const void* x_split, const float* x_nchw, int64_t sn, int64_t sc, int64_t M, int Cin, const void* wp0, const float* b0,
-                  const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride, const float* gm,
-                  int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
-                  void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int wcmc_embed3_bwd(const void* x_split, const float* x_nchw, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M,
+                               int Cin, const void* wp0, const float* b0, const void* wp1, const float* b1, const void* wt1,
+                               const void* wt2, const float* gy, int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S,
+                               int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
+                               void* workspace, size_t workspace_bytes, void* stream) {
   E3Params p = {};
-  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, sn, sc, HW)) return rc;
+  if (int rc = e3_fill(p, x_split, M, Cin, wp0, b0, wp1, b1, x_nchw, x_sample_stride, x_channel_stride, HW)) return rc;
   WCMC_REQUIRE(wt1 && wt2 && (gy || gm) && dw0 && db0 && dw1 && db1 && dw2 && db2 && workspace && aligned16(wt1) && aligned16(wt2) &&
                    (!gy || aligned16(gy)) && (!gm || aligned16(gm)) && aligned16(workspace),
                WCMC_ERR_BAD_ARG, "embed3_bwd: bad argument");
@@ -1361,26 +1142,6 @@ static int e3_bwd(const void* x_split, const float* x_nchw, int64_t sn, int64_t 
   return check_launch("embed3_bwd_finish");
 }
 
-extern "C" int wcmc_embed3_bwd(const void* x_split, int64_t M, int Cin, const void* wp0, const float* b0, const void* wp1,
-                               const float* b1, const void* wt1, const void* wt2, const float* gy, int gy_pixel_stride,
-                               const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  WCMC_REQUIRE(x_split, WCMC_ERR_BAD_ARG, "embed3: bad argument");
-  return e3_bwd(x_split, nullptr, 0, 0, M, Cin, wp0, b0, wp1, b1, wt1, wt2, gy, gy_pixel_stride, gm, gm_pixel_stride, S, HW, gm_scale, dw0, db0,
-                dw1, db1, dw2, db2, workspace, workspace_bytes, stream);
-}
-
-extern "C" int wcmc_embed3_bwd_nchw(const float* x, int64_t x_sample_stride, int64_t x_channel_stride, int64_t M, int Cin, const void* wp0,
-                                    const float* b0, const void* wp1, const float* b1, const void* wt1, const void* wt2, const float* gy,
-                                    int gy_pixel_stride, const float* gm, int gm_pixel_stride, int S, int64_t HW, float gm_scale, float* dw0,
-                                    float* db0, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  WCMC_REQUIRE(x, WCMC_ERR_BAD_ARG, "embed3: bad argument");
-  return e3_bwd(nullptr, x, x_sample_stride, x_channel_stride, M, Cin, wp0, b0, wp1, b1, wt1, wt2, gy, gy_pixel_stride, gm, gm_pixel_stride, S, HW,
-                gm_scale, dw0, db0, dw1, db1, dw2, db2, workspace, workspace_bytes, stream);
-}
-
-
 // ---------------------------------------------------------------- PathNet.final, fused
 extern "C" int wcmc_final2_supported(int C1, int C2, int Chid, int outc, int64_t HW) {
   return C1 == 64 && C2 == 64 && Chid == 128 && outc >= 1 && outc <= 8 && HW > 0 && HW % 64 == 0;
@@ -1402,30 +1163,17 @@ static int f2_fill(F2Params& p, const float* y, int y_ps, const float* prop, int
   return 0;
 }
 
-// save: h's hi plane leaves with out (wcmc_final2_fwd_save); always final2_kernel<false> then -- the wave-private experiment writes no plane
-static int f2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW, const void* wp0,
-                  const float* b0, const void* wp1, const float* b1, int outc, float* out, bool save, void* h_hi, void* stream) {
+// h_hi non-null: h's hi plane leaves with out, for the backward that reads both
+extern "C" int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
+                               void* stream) {
   F2Params p = {};
   if (int rc = f2_fill(p, y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc)) return rc;
   WCMC_REQUIRE(out && aligned16(out), WCMC_ERR_BAD_ARG, "final2_fwd: bad output");
   p.out = out;
-  if (save) {
-    WCMC_REQUIRE(h_hi, WCMC_ERR_BAD_ARG, "final2_fwd_save: null h_hi");
-    WCMC_REQUIRE(aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_fwd_save: h_hi must be 16-byte aligned");
+  if (h_hi) {
+    WCMC_REQUIRE(aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_fwd: h_hi must be 16-byte aligned");
     p.hsave = (u16*)h_hi; p.h_bytes = (unsigned)((int64_t)B * S * HW * 256);      // (< 2 GiB: f2_fill)
-  } else {
-    const char* e = ab_env("WCMC_F2W");                     // (debug build) 0: the cout-tile-per-wave kernel of round 3; 2: 32 pixels per wave; 1: 16
-    if (e && e[0] != '0') {
-      const int ni = e[0] == '2' ? 2 : 1;
-      static LdsAttr attrw1, attrw2;
-      if (set_max_lds(ni == 2 ? reinterpret_cast<const void*>(&final2w_fwd_kernel<2>) : reinterpret_cast<const void*>(&final2w_fwd_kernel<1>),
-                      (size_t)F2W_LDS_FWD, ni == 2 ? attrw2 : attrw1) != hipSuccess) return WCMC_ERR_LAUNCH;
-      const int64_t nunits = (int64_t)B * (HW / (16 * ni)), nb = (nunits + 7) / 8;
-      const int cap = ni == 2 ? f2_grid() : 2 * f2_grid();
-      if (ni == 2) hipLaunchKernelGGL(final2w_fwd_kernel<2>, dim3((unsigned)(nb < cap ? nb : cap)), dim3(512), F2W_LDS_FWD, (hipStream_t)stream, p);
-      else hipLaunchKernelGGL(final2w_fwd_kernel<1>, dim3((unsigned)(nb < cap ? nb : cap)), dim3(512), F2W_LDS_FWD, (hipStream_t)stream, p);
-      return check_launch("final2_fwd (wave-private)");
-    }
   }
   static LdsAttr attr;
   if (set_max_lds(reinterpret_cast<const void*>(&final2_kernel<false>), (size_t)F2_LDS_FWD, attr) != hipSuccess) return WCMC_ERR_LAUNCH;
@@ -1434,30 +1182,20 @@ static int f2_fwd(const float* y, int y_pixel_stride, const float* prop, int pro
   return check_launch("final2_fwd");
 }
 
-extern "C" int wcmc_final2_fwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* stream) {
-  return f2_fwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, out, false, nullptr, stream);
-}
-extern "C" int wcmc_final2_fwd_save(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                                    const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, float* out, void* h_hi,
-                                    void* stream) {
-  return f2_fwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, out, true, h_hi, stream);
-}
-
-// saved: the backward on the forward's out and h_hi (wcmc_final2_bwd_saved); else the recomputing one
-static int f2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                  const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                  const void* wt1, const float* gout, bool saved, const float* out, const void* h_hi, float* dy, float* dprop, float* dw0,
-                  float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream) {
+// out and h_hi non-null: the backward on the forward's out and h_hi; both null: the recomputing one
+extern "C" int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
+                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
+                               const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
+                               float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream) {
   F2Params p = {};
   if (int rc = f2_fill(p, y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc)) return rc;
   WCMC_REQUIRE(wt0 && wt1 && gout && dy && dprop && dw0 && db0 && dw1 && db1 && workspace && aligned16(wt0) && aligned16(wt1) &&
                    aligned16(gout) && aligned16(dy) && aligned16(dprop) && aligned16(workspace),
                WCMC_ERR_BAD_ARG, "final2_bwd: bad argument");
-  if (saved) {
-    WCMC_REQUIRE(out && h_hi, WCMC_ERR_BAD_ARG, "final2_bwd_saved: null out or h_hi");
-    WCMC_REQUIRE(aligned16(out) && aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_bwd_saved: out and h_hi must be 16-byte aligned");
-  }
+  WCMC_REQUIRE(!out || h_hi, WCMC_ERR_BAD_ARG, "final2_bwd: out without h_hi (the forward's tensors come as a pair, or not at all)");
+  WCMC_REQUIRE(!h_hi || out, WCMC_ERR_BAD_ARG, "final2_bwd: h_hi without out (the forward's tensors come as a pair, or not at all)");
+  const bool saved = out != nullptr;
+  WCMC_REQUIRE(aligned16(out) && aligned16(h_hi), WCMC_ERR_ALIGNMENT, "final2_bwd: out and h_hi must be 16-byte aligned");
   WCMC_REQUIRE(workspace_bytes >= wcmc_final2_bwd_workspace_bytes(), WCMC_ERR_WORKSPACE, "final2_bwd: workspace too small");
   p.wt0 = (const u16*)wt0; p.wt1 = (const u16*)wt1; p.gout = gout; p.dy = dy; p.dprop = dprop; p.ws = (float*)workspace;
   const int64_t M = (int64_t)B * S * HW;
@@ -1477,19 +1215,4 @@ static int f2_bwd(const float* y, int y_pixel_stride, const float* prop, int pro
   hipLaunchKernelGGL(final2_bwd_finish_kernel, dim3((unsigned)((F2_WS_PER_BLOCK + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float*)workspace, nblk, outc, dw0, db0, dw1, db1);
   return check_launch("final2_bwd_finish");
-}
-
-extern "C" int wcmc_final2_bwd(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                               const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                               const void* wt1, const float* gout, float* dy, float* dprop, float* dw0, float* db0, float* dw1,
-                               float* db1, void* workspace, size_t workspace_bytes, void* stream) {
-  return f2_bwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, wt0, wt1, gout, false, nullptr, nullptr, dy, dprop,
-                dw0, db0, dw1, db1, workspace, workspace_bytes, stream);
-}
-extern "C" int wcmc_final2_bwd_saved(const float* y, int y_pixel_stride, const float* prop, int prop_pixel_stride, int B, int S, int64_t HW,
-                                     const void* wp0, const float* b0, const void* wp1, const float* b1, int outc, const void* wt0,
-                                     const void* wt1, const float* gout, const float* out, const void* h_hi, float* dy, float* dprop,
-                                     float* dw0, float* db0, float* dw1, float* db1, void* workspace, size_t workspace_bytes, void* stream) {
-  return f2_bwd(y, y_pixel_stride, prop, prop_pixel_stride, B, S, HW, wp0, b0, wp1, b1, outc, wt0, wt1, gout, true, out, h_hi, dy, dprop,
-                dw0, db0, dw1, db1, workspace, workspace_bytes, stream);
 }

@@ -82,7 +82,7 @@ EMBED_IN_PLACE = os.environ.get("WCMC_EMBED_IN_PLACE", "1") != "0"
 FUSE_FINAL = os.environ.get("WCMC_FUSE_FINAL", "1") != "0"
 
 # The fused final chain's forward hands the hi plane of its hidden activation (bf16, 256 B per pixel) and its output to the backward
-# (wcmc_final2_fwd_save / _bwd_saved) instead of the backward recomputing both (wcmc_final2_bwd): same results bit for bit, 60 of
+# (h_hi / out of wcmc_final2_fwd / _bwd) instead of the backward recomputing both (null pointers there): same results bit for bit, 60 of
 # 118 MFMAs per tile and wave fewer, +268 MB live per PathNet between forward and backward at the benchmark shape.  False: recompute.
 SAVE_FINAL_HIDDEN = True
 

@@ -23,7 +23,7 @@ def _dense_pixel_stride(g):
 
 def embed_in_place_supported(x, widths=(64, 64, 64)):
     """True when the fused embedding chain (layer widths ``widths``) will read the channel-first fp32 tensor `x` where it lies
-    (``wcmc_embed3_*_nchw``): the switches, the mode, the chain's channel counts and ``wcmc_embed3_nchw_supported`` on x's shape
+    (the ``x_nchw`` form of ``wcmc_embed3_mean_fwd`` / ``_bwd``): the switches, the mode, the chain's channel counts and ``wcmc_embed3_nchw_supported`` on x's shape
     and strides.  Launches nothing and needs no device."""
     if not (_sw.EMBED_IN_PLACE and _sw.FUSE_EMBED and _sw.DEBUG_ACTS is None and _sw.reduced_backward()):
         return False
@@ -52,7 +52,7 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
     """``y = chain3(x); m = y.view(B,S,...).mean(1)`` (networks.py:33-36) with the three 1x1 layers in ONE launch
     (``wcmc_embed3_fwd``) and a backward that recomputes the hidden activations (``wcmc_embed3_bwd``): nothing but x, y and
     the two gradients of y ever touches HBM.  x: an NHWC view or a tensor with its split attached (``_split_shared``), or a
-    channel-first tensor tagged by ``embed_in_place``, which both launches read where it lies (``wcmc_embed3_*_nchw``)."""
+    channel-first tensor tagged by ``embed_in_place``, which both launches read where it lies (their ``x_nchw`` argument)."""
 
     @staticmethod
     def forward(ctx, x, s, *params):
@@ -66,16 +66,15 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
         m = nhwc_empty(n // s, 64, h, w, y.device)
         wb = (_ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), _ptr(packs[2][0]),
               _ptr(params[5].detach()))
-        if in_place:            # (HW % 64 == 0: the mean always leaves with y)
-            with _Timed("embed3_fwd", 4.0 * n * h * w * (cin + 64 + 64 // s), "byte"):
-                check(lib().wcmc_embed3_mean_fwd_nchw(_ptr(xs), xs.stride(0), xs.stride(1), n * h * w, cin, *wb, _ptr(y), _ptr(m), s, h * w,
-                                                      _stream()), "embed3_mean_fwd_nchw")
-        elif lib().wcmc_embed3_mean_supported(s, h * w):
+        # the source, as (x_split, x_nchw, sample stride, channel stride), and the floats per pixel the launches read of it
+        src = (_ptr(None), _ptr(xs), xs.stride(0), xs.stride(1)) if in_place else (_ptr(xs), _ptr(None), 0, 0)
+        xf = cin if in_place else (cin + 7) // 8 * 8
+        if in_place or lib().wcmc_embed3_mean_supported(s, h * w):          # (in place: HW % 64 == 0)
             # the mean leaves with y (the kernel walks the S samples of a pixel tile and keeps their sum in registers)
-            with _Timed("embed3_fwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64 + 64 // s), "byte"):
-                check(lib().wcmc_embed3_mean_fwd(_ptr(xs), n * h * w, cin, *wb, _ptr(y), _ptr(m), s, h * w, _stream()), "embed3_mean_fwd")
+            with _Timed("embed3_fwd", 4.0 * n * h * w * (xf + 64 + 64 // s), "byte"):
+                check(lib().wcmc_embed3_mean_fwd(*src, n * h * w, cin, *wb, _ptr(y), _ptr(m), s, h * w, _stream()), "embed3_mean_fwd")
         else:
-            with _Timed("embed3_fwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64), "byte"):
+            with _Timed("embed3_fwd", 4.0 * n * h * w * (xf + 64), "byte"):
                 check(lib().wcmc_embed3_fwd(_ptr(xs), n * h * w, cin, *wb, _ptr(y), _stream()), "embed3_fwd")
             check(lib().wcmc_spp_reduce(*_v(y), *_v(m), n // s, s, h, w, 64, 1.0 / s, _stream()), "spp_reduce")
         ctx.s, ctx.dims, ctx.in_place = s, (n, cin, h, w), in_place
@@ -100,15 +99,13 @@ class _EmbedSppMeanFusedX(torch.autograd.Function):
         nb = lib().wcmc_embed3_bwd_workspace_bytes()
         ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         packs = ctx.packs
-        rest = (n * h * w, cin, _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), _ptr(packs[1][1]), _ptr(packs[2][1]),
-                _ptr(gy), _dense_pixel_stride(gy) if gy is not None else 0, _ptr(gm), _dense_pixel_stride(gm) if gm is not None else 0,
-                s, h * w, 1.0 / s, _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nb, _stream())
-        if ctx.in_place:
-            with _Timed("embed3_bwd", 4.0 * n * h * w * (cin + 64 + (64 // s if gm is not None else 0)), "byte"):
-                check(lib().wcmc_embed3_bwd_nchw(_ptr(xs), xs.stride(0), xs.stride(1), *rest), "embed3_bwd_nchw")
-        else:
-            with _Timed("embed3_bwd", 4.0 * n * h * w * ((cin + 7) // 8 * 8 + 64 + (64 // s if gm is not None else 0)), "byte"):
-                check(lib().wcmc_embed3_bwd(_ptr(xs), *rest), "embed3_bwd")
+        src = (_ptr(None), _ptr(xs), xs.stride(0), xs.stride(1)) if ctx.in_place else (_ptr(xs), _ptr(None), 0, 0)
+        xf = cin if ctx.in_place else (cin + 7) // 8 * 8
+        with _Timed("embed3_bwd", 4.0 * n * h * w * (xf + 64 + (64 // s if gm is not None else 0)), "byte"):
+            check(lib().wcmc_embed3_bwd(*src, n * h * w, cin, _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), _ptr(packs[1][1]),
+                                        _ptr(packs[2][1]), _ptr(gy), _dense_pixel_stride(gy) if gy is not None else 0, _ptr(gm),
+                                        _dense_pixel_stride(gm) if gm is not None else 0, s, h * w, 1.0 / s, _ptr(dw0), _ptr(db0),
+                                        _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nb, _stream()), "embed3_bwd")
         return (None, None, dw0, db0, dw1, db1, dw2, db2)
 
 
@@ -116,8 +113,8 @@ class _FinalFusedX(torch.autograd.Function):
     """``chain2(cat([flat, repeat_S(prop)], 1))`` (networks.py:39-42) as one launch per direction (``wcmc_final2_*``): the
     128-channel concatenation is never written.  Of the hidden activation the backward needs the bf16 hi plane only and of the
     output its sign: with ``ops.SAVE_FINAL_HIDDEN`` a forward that a backward will follow writes that plane ([M][128] bf16)
-    beside the output and the backward reads both (``wcmc_final2_fwd_save`` / ``_bwd_saved``); otherwise nothing is kept and the
-    backward recomputes the chain (``wcmc_final2_bwd``).  Same results bit for bit."""
+    beside the output and the backward reads both (``h_hi`` / ``out, h_hi`` of the two entries); otherwise nothing is kept and the
+    backward recomputes the chain (null pointers there).  Same results bit for bit."""
 
     @staticmethod
     def forward(ctx, flat, prop, s, *params):
@@ -128,18 +125,16 @@ class _FinalFusedX(torch.autograd.Function):
         packs = _pack_chain_x([params[0], params[2]], 1)
         osz = 4 if outc <= 4 else 8                           # pixel stride of the output: round_up(outc, 4)
         buf = torch.empty((bs, h, w, osz), device=flat.device, dtype=torch.float32)
-        args = (_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
-                _ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), outc, _ptr(buf))
-        saved = ()
+        hhi = None
         if _sw.SAVE_FINAL_HIDDEN and any(ctx.needs_input_grad):
             # h's hi plane: 128 bf16 = 64 floats' worth of bytes per pixel, written here and read once by the backward
             hhi = torch.empty((bs * h * w, 128), device=flat.device, dtype=torch.bfloat16)
-            with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz + 64), "byte"):
-                check(lib().wcmc_final2_fwd_save(*args, _ptr(hhi), _stream()), "final2_fwd_save")
-            saved = (hhi, buf)       # (buf through save_for_backward: its version counter guards the output the caller holds)
-        else:
-            with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz), "byte"):
-                check(lib().wcmc_final2_fwd(*args, _stream()), "final2_fwd")
+        with _Timed("final2_fwd", 4.0 * bs * h * w * (64 + 64 // s + osz + (64 if hhi is not None else 0)), "byte"):
+            check(lib().wcmc_final2_fwd(_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
+                                        _ptr(packs[0][0]), _ptr(params[1].detach()), _ptr(packs[1][0]), _ptr(params[3].detach()), outc,
+                                        _ptr(buf), _ptr(hhi), _stream()), "final2_fwd")
+        # (buf through save_for_backward: its version counter guards the output the caller holds)
+        saved = (hhi, buf) if hhi is not None else ()
         ctx.geom, ctx.packs = (b, s, h, w, outc), packs
         ctx.save_for_backward(flat, prop, *params, *saved)
         return buf.permute(0, 3, 1, 2)[:, :outc]
@@ -160,16 +155,12 @@ class _FinalFusedX(torch.autograd.Function):
         nb = lib().wcmc_final2_bwd_workspace_bytes()
         ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         packs = ctx.packs
-        ins = (_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
-               _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), outc, _ptr(packs[0][1]), _ptr(packs[1][1]), _ptr(g))
-        outs = (_ptr(dy), _ptr(dprop), _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1), _ptr(ws), nb, _stream())
-        if saved:
-            hhi, buf = saved
-            with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s + 64 + osz), "byte"):
-                check(lib().wcmc_final2_bwd_saved(*ins, _ptr(buf), _ptr(hhi), *outs), "final2_bwd_saved")
-        else:
-            with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s), "byte"):
-                check(lib().wcmc_final2_bwd(*ins, *outs), "final2_bwd")
+        hhi, buf = saved if saved else (None, None)
+        with _Timed("final2_bwd", 4.0 * b * s * h * w * (64 + 64 // s + osz + 64 + 64 // s + (64 + osz if saved else 0)), "byte"):
+            check(lib().wcmc_final2_bwd(_ptr(flat), _dense_pixel_stride(flat), _ptr(prop), _dense_pixel_stride(prop), b, s, h * w,
+                                        _ptr(packs[0][0]), _ptr(b0), _ptr(packs[1][0]), _ptr(b1), outc, _ptr(packs[0][1]), _ptr(packs[1][1]),
+                                        _ptr(g), _ptr(buf), _ptr(hhi), _ptr(dy), _ptr(dprop), _ptr(dw0), _ptr(db0), _ptr(dw1), _ptr(db1),
+                                        _ptr(ws), nb, _stream()), "final2_bwd")
         return (dy if ctx.needs_input_grad[0] else None, dprop if ctx.needs_input_grad[1] else None, None, dw0, db0, dw1, db1)
 
 
