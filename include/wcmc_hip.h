@@ -865,6 +865,26 @@ int wcmc_pbuffer_filter(const float* image, int64_t ish, int64_t isw, int64_t is
                         const void* mask, int mask_bytes, float* out, float* wsum, void* workspace, size_t workspace_bytes,
                         int H, int W, int S, int C, int Cr, int R, int f, float bandwidth, float eps, int passes, void* stream);
 
+/* ---------------------------------------------------------------- structural-similarity training loss (csrc/dssim_loss.hip)
+ * loss = 1 - mean SSIM over every 7x7 window of every plane of a strided fp32 (N,C,H,W) pair; the build's own specification:
+ * DESIGN.md section 23 (the SSIM of section 10 / wcmc_image_eval: uniform window at valid positions, K1 0.01, K2 0.03, sample
+ * covariance 49/48, C1 = (K1 R)^2, C2 = (K2 R)^2 with R = data_range > 0).  Element (n,c,y,x) of x is x[n*xsn + c*xsc + y*xsh + x*xsw].
+ *   tonemap 0  none
+ *   tonemap 1  reinhard: T(v) = max(v, 0) / (1 + max(v, 0)) on both images (metrics._tonemap); T'(v) = 1 / (1 + v)^2 for v >= 0, else 0
+ * With tonemap 1, data_range 2, N = 1, C = 3 the loss is the `_tonemap` DSSIM of wcmc_image_eval.  H, W >= 7, N * C <= 65535.
+ * Every moment, the SSIM map and the gradient's box sums are fp64; partial sums are added in a fixed order by a one-block finish (no
+ * atomics: loss and dx are bitwise reproducible).  Non-finite inputs are not filtered: a NaN pixel gives a NaN loss.
+ *   fwd: *loss (fp32, device) <- the loss.  workspace: wcmc_dssim_loss_workspace_bytes(N, C, H, W) bytes (0 for a refused shape).
+ *   bwd: dx (contiguous (N,C,H,W)) = *grad_loss * d loss / d x; ref carries no gradient.  The backward recomputes the per-window
+ *        coefficients from the inputs: nothing but x and ref passes from fwd to bwd. */
+size_t wcmc_dssim_loss_workspace_bytes(int N, int C, int H, int W);
+int wcmc_dssim_loss_fwd(const float* x, int64_t xsn, int64_t xsc, int64_t xsh, int64_t xsw, const float* ref, int64_t rsn,
+                        int64_t rsc, int64_t rsh, int64_t rsw, int tonemap, double data_range, float* loss, void* workspace,
+                        size_t workspace_bytes, int N, int C, int H, int W, void* stream);
+int wcmc_dssim_loss_bwd(const float* x, int64_t xsn, int64_t xsc, int64_t xsh, int64_t xsw, const float* ref, int64_t rsn,
+                        int64_t rsc, int64_t rsh, int64_t rsw, int tonemap, double data_range, const float* grad_loss, float* dx,
+                        int N, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,9 @@ SIGNATURES = {
     "wcmc_blend_finish": (I, [P, P, I, I, I, P, P]),
     "wcmc_pbuffer_filter_workspace_bytes": (Z, [I, I, I, I]),
     "wcmc_pbuffer_filter": (I, [P, L, L, L, P, L, L, L, L, P, I, P, P, P, Z, I, I, I, I, I, I, I, F, F, I, P]),
+    "wcmc_dssim_loss_workspace_bytes": (Z, [I, I, I, I]),
+    "wcmc_dssim_loss_fwd": (I, [P, L, L, L, L, P, L, L, L, L, I, D, P, P, Z, I, I, I, I, P]),
+    "wcmc_dssim_loss_bwd": (I, [P, L, L, L, L, P, L, L, L, L, I, D, P, P, I, I, I, I, P]),
 }
 
 _lib = None

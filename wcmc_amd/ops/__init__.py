@@ -170,7 +170,8 @@ from .pathnet_fused import (_dense_pixel_stride, _EmbedSppMeanFusedX, _FinalFuse
                             _note_unfused, conv_chain_spp_mean, cat_broadcast_chain, embed_in_place, embed_in_place_supported,
                             _reads_in_place)
 from .image import (_KernelApply, kernel_apply, chain_kernel_apply, _Recombine, recombine, _image_loss_raw, _L1Mean, l1_mean,  # noqa: E402,F401
-                    image_metrics, relative_mse, LOSS2_KINDS, _ImageLoss2, image_loss2, image_eval)
+                    image_metrics, relative_mse, LOSS2_KINDS, _ImageLoss2, image_loss2, DSSIM_TONEMAPS, dssim_loss_supported,
+                    _DssimLoss, dssim_loss, image_eval)
 from .splat import (SPLAT_SOFTMAX, SPLAT_SHIFT, _splat_dims, _KernelSplat, kernel_splat, logit_max)  # noqa: E402,F401
 from .filter import (PBF_STATS, PBF_FILTER, PBF_MAX_RADIUS, PBF_MAX_PATCH_RADIUS, PBF_MAX_CHANNELS,  # noqa: E402,F401
                      PBF_MAX_IMAGE_CHANNELS, _pbuffer_filter_check, pbuffer_filter)

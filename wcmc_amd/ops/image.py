@@ -1,4 +1,5 @@
-"""Kernel apply (csrc/kernel_apply.hip), recombination, the image losses and the full-frame evaluation (csrc/image_eval.hip)."""
+"""Kernel apply (csrc/kernel_apply.hip), recombination, the image losses (pointwise, and the structural one of csrc/dssim_loss.hip)
+and the full-frame evaluation (csrc/image_eval.hip)."""
 import torch
 
 from .._lib import check, lib
@@ -166,6 +167,56 @@ class _ImageLoss2(torch.autograd.Function):
 def image_loss2(x, ref, kind, eps=1e-2):
     """kind: 'smape' | 'tonemapped_mse' | 'tonemapped_relative_mse'; differentiable in x."""
     return _ImageLoss2.apply(x, ref.detach(), LOSS2_KINDS[kind], eps)
+
+
+DSSIM_TONEMAPS = {"none": 0, "reinhard": 1}
+
+
+def dssim_loss_supported(n, c, h, w):
+    """Does ``wcmc_dssim_loss_*`` take an (n, c, h, w) pair?  (A 7x7 window must fit; the planes must fit one grid.)"""
+    return lib().wcmc_dssim_loss_workspace_bytes(n, c, h, w) > 0
+
+
+class _DssimLoss(torch.autograd.Function):
+    """1 - mean SSIM over every 7x7 window of every plane (csrc/dssim_loss.hip): one pass + a one-block finish
+    forward, one pass backward that recomputes the per-window coefficients from the saved inputs; ref carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, ref, tonemap, data_range):
+        _need_cuda(x, ref)
+        if x.dim() != 4 or x.shape != ref.shape:
+            raise ValueError("dssim_loss: x and ref must be (N, C, H, W) of one size (got %s and %s)" % (tuple(x.shape), tuple(ref.shape)))
+        if x.dtype != torch.float32 or ref.dtype != torch.float32:
+            raise TypeError("dssim_loss: x and ref must be float32 (got %s and %s)" % (x.dtype, ref.dtype))
+        n, c, h, w = x.shape
+        nbytes = lib().wcmc_dssim_loss_workspace_bytes(n, c, h, w)
+        ws = torch.empty(max(1, (nbytes + 7) // 8), device=x.device, dtype=torch.float64)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        check(lib().wcmc_dssim_loss_fwd(_ptr(x), *x.stride(), _ptr(ref), *ref.stride(), tonemap, float(data_range), _ptr(loss),
+                                        _ptr(ws), nbytes, n, c, h, w, _stream()), "dssim_loss_fwd")
+        ctx.save_for_backward(x, ref)
+        ctx.tonemap, ctx.data_range = tonemap, float(data_range)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, ref = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dx = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
+        g = g.contiguous()
+        check(lib().wcmc_dssim_loss_bwd(_ptr(x), *x.stride(), _ptr(ref), *ref.stride(), ctx.tonemap, ctx.data_range, _ptr(g), _ptr(dx),
+                                        n, c, h, w, _stream()), "dssim_loss_bwd")
+        return dx, None, None, None
+
+
+def dssim_loss(x, ref, tonemap="reinhard", data_range=2.0):
+    """1 - mean SSIM (7x7 uniform windows at valid positions, K1 0.01, K2 0.03, sample covariance) of two fp32 (N,C,H,W) tensors of
+    any strides, H, W >= 7; differentiable in x.  tonemap: 'none' | 'reinhard' (``metrics._tonemap`` on both images).  With
+    'reinhard', data_range 2 and one 3-channel frame this is the ``_tonemap`` DSSIM of ``image_eval``.  A shape the kernel refuses
+    raises; NaN pixels give a NaN loss."""
+    if tonemap not in DSSIM_TONEMAPS:
+        raise ValueError("dssim_loss: tonemap %r is not one of %s" % (tonemap, sorted(DSSIM_TONEMAPS)))
+    return _DssimLoss.apply(x, ref.detach(), DSSIM_TONEMAPS[tonemap], data_range)
 
 
 # ------------------------------------------------------------------------------------------------- full-frame evaluation

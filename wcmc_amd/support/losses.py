@@ -12,7 +12,7 @@ import torch
 from .. import ops
 
 __all__ = ["GlobalRelativeSimilarityLoss", "FeatureMSE", "RelativeMSE", "SMAPE", "TonemappedMSE",
-           "TonemappedRelativeMSE"]
+           "TonemappedRelativeMSE", "DSSIM", "WithDSSIM"]
 
 
 class FeatureMSE(torch.nn.Module):
@@ -180,16 +180,18 @@ class RelativeMSE(torch.nn.Module):
 _REFUSED = set()
 
 
-def _hip_image(im, ref, who="image loss"):
+def _hip_image(im, ref, who="image loss", also=None):
     """The HIP loss kernels take fp32 (N,C,H,W) CUDA images whose reference carries no gradient (every call site of the reference:
     ``interfaces.py:418-421, 815-818``).  CPU tensors (the host-logic tests) take the torch expression; a CUDA tensor the kernels
-    refuse takes it too, but not silently: one warning per class and reason."""
+    refuse takes it too, but not silently: one warning per class and reason.  also: a further refusal of the
+    calling class, ``also(im)`` -> reason or None, asked once the common ones have passed."""
     if not im.is_cuda:
         return False
     why = ("a %d-D image" % im.dim() if im.dim() != 4 else
            "dtype %s / %s" % (im.dtype, ref.dtype) if im.dtype != torch.float32 or ref.dtype != torch.float32 else
            "shapes %s vs %s" % (tuple(im.shape), tuple(ref.shape)) if ref.shape != im.shape else
-           "a reference that requires a gradient" if ref.requires_grad else None)
+           "a reference that requires a gradient" if ref.requires_grad else
+           also(im) if also is not None else None)
     if why is None:
         return True
     if (who, why) not in _REFUSED:
@@ -245,3 +247,60 @@ class TonemappedRelativeMSE(torch.nn.Module):
             return ops.image_loss2(im, ref, "tonemapped_relative_mse", self.eps)
         im, ref = _reinhard(im), _reinhard(ref)
         return 0.5 * torch.mean(torch.pow(im - ref, 2) / (torch.pow(ref, 2) + self.eps))
+
+
+def _dssim_torch(im, ref, tonemap, data_range):
+    """DESIGN.md section 23 in torch ops (``F.avg_pool2d`` moments): what CPU tensors and refused CUDA tensors take."""
+    import torch.nn.functional as F
+    if tonemap == 'reinhard':
+        im, ref = _reinhard(im), _reinhard(ref)
+    cov, c1, c2 = 49.0 / 48.0, (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    pool = lambda z: F.avg_pool2d(z, 7, stride=1)                        # noqa: E731
+    mx, my = pool(im), pool(ref)
+    vx, vy, vxy = cov * (pool(im * im) - mx * mx), cov * (pool(ref * ref) - my * my), cov * (pool(im * ref) - mx * my)
+    s = ((2 * mx * my + c1) * (2 * vxy + c2)) / ((mx * mx + my * my + c1) * (vx + vy + c2))
+    return 1 - s.mean()
+
+
+class DSSIM(torch.nn.Module):
+    """1 - mean SSIM over 7x7 uniform windows at valid positions (K1 0.01, K2 0.03, sample covariance), of the
+    Reinhard tone-mapped images by default: with ``data_range`` 2 the DSSIM column ``evaluate`` reports under ``_tonemap``.  An
+    addition of this build (the reference trains on pointwise losses alone)."""
+
+    def __init__(self, tonemap='reinhard', data_range=2.0):
+        super(DSSIM, self).__init__()
+        if tonemap not in ops.DSSIM_TONEMAPS:
+            raise ValueError("DSSIM: tonemap %r is not one of %s" % (tonemap, sorted(ops.DSSIM_TONEMAPS)))
+        if not data_range > 0:
+            raise ValueError("DSSIM: data_range should be positive (got %r)" % (data_range,))
+        self.tonemap, self.data_range = tonemap, float(data_range)
+
+    @staticmethod
+    def _refused(im):
+        return None if ops.dssim_loss_supported(*im.shape) else "a %d x %d x %d x %d image" % tuple(im.shape)
+
+    def forward(self, im, ref):
+        if _hip_image(im, ref, "DSSIM", self._refused):
+            return ops.dssim_loss(im, ref, self.tonemap, self.data_range)
+        return _dssim_torch(im, ref, self.tonemap, self.data_range)
+
+
+class WithDSSIM(torch.nn.Module):
+    """``(1 - weight) * base(im, ref) + weight * DSSIM(im, ref)``: a pointwise image loss mixed with the structural term
+    (``--dssim_weight`` of the launchers).  A plain ``nn.L1Loss`` base on an fp32 (N,C,H,W) CUDA image runs as ``ops.l1_mean``,
+    as it does un-mixed (``interfaces._l1``)."""
+
+    def __init__(self, base, weight, tonemap='reinhard', data_range=2.0):
+        super(WithDSSIM, self).__init__()
+        if not 0.0 <= weight <= 1.0:
+            raise ValueError("WithDSSIM: weight should be in [0, 1] (got %r)" % (weight,))
+        self.base, self.weight = base, float(weight)
+        self.dssim = DSSIM(tonemap, data_range)
+
+    def forward(self, im, ref):
+        if type(self.base) is torch.nn.L1Loss and self.base.reduction == 'mean' and im.is_cuda and im.dim() == 4 and \
+                im.dtype == torch.float32 and im.shape == ref.shape:
+            base = ops.l1_mean(im, ref)
+        else:
+            base = self.base(im, ref)
+        return (1.0 - self.weight) * base + self.weight * self.dssim(im, ref)

@@ -37,7 +37,7 @@ from . import distributed as wd
 from .optim import FusedClipAdam
 from .support import checkpoint as ckpt
 from .support.interfaces import KPCNInterface, KPCNPreInterface, KPCNRefInterface
-from .support.losses import FeatureMSE, GlobalRelativeSimilarityLoss, RelativeMSE
+from .support.losses import FeatureMSE, GlobalRelativeSimilarityLoss, RelativeMSE, WithDSSIM
 from .support.networks import PathNet
 from .synthetic import make_batch
 
@@ -290,6 +290,7 @@ def init_model(sizes, args, device, group=None):
                 print('Manifold loss: Global Relative Similarity')
         else:
             print('Manifold loss: None (i.e., ablation study)')
+        with_dssim(args, loss_funcs, ('l_diffuse', 'l_specular', 'l_recon'))
         if args.kpcn_ref:
             itf = KPCNRefInterface(models, optims, loss_funcs, args, train_branches=args.train_branches)
         elif args.kpcn_pre:
@@ -395,12 +396,13 @@ MULTI_SPP_EPILOG = ('additions of this build, on train_kpcn, train_sbmc and trai
                     'and validate at every sample count 2..--num_samples) and --ms_window K (images kept on the device while the '
                     'counts are walked over them; default %d); --augment (with --from_data_dir: every training patch under one of '
                     'the eight flips / quarter turns of the square, drawn uniformly; validation is never augmented) and '
-                    '--augment_seed N (seed of that draw, a random stream of its own; default 0)' % MS_WINDOW)
+                    '--augment_seed N (seed of that draw, a random stream of its own; default 0); --dssim_weight A (mix the '
+                    'structural loss DSSIM into the image losses with weight A in [0, 1]; default 0: off)' % MS_WINDOW)
 
 
 def multi_spp_parser():
     """``--multi_spp`` / ``--ms_window`` (the reference always trains over 2..spp, ``train_kpcn.py:170-173``) and ``--augment`` /
-    ``--augment_seed``: additions of this build.
+    ``--augment_seed`` and ``--dssim_weight`` (section 23): additions of this build.
     A parser of their own, read before the launcher's: ``build_parser()`` of each launcher stays the reference's flag surface plus
     what earlier rounds added, which tests pin flag by flag."""
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
@@ -418,6 +420,13 @@ def multi_spp_parser():
     p.add_argument('--augment_seed', type=int, default=None, metavar='N',
                    help='an addition of this build; with --augment: seed of the transform draw, a random stream of its own '
                         '(default 0); the patch origins do not depend on it')
+    p.add_argument('--dssim_weight', type=float, default=0.0, metavar='A',
+                   help='an addition of this build; A in [0, 1], default 0 (off: the losses are exactly those of the reference).  With '
+                        'A > 0 every image loss the step trains on becomes (1 - A) * loss + A * DSSIM, DSSIM = 1 - mean SSIM of the '
+                        'Reinhard tone-mapped images over 7x7 windows, the DSSIM column `evaluate` reports under `_tonemap` '
+                        '(train_kpcn: l_diffuse, l_specular and l_recon; train_sbmc / train_lbmc: l_recon; l_test and l_manif never).  '
+                        'The logged l_diffuse, l_specular and l_total are then the MIXED values.  Nobody has tuned A on a trained '
+                        'model: no value is recommended')
     return p
 
 
@@ -457,10 +466,29 @@ def check_augment_args(args):
         args.augment_seed = 0
 
 
+def check_dssim_args(args):
+    a = getattr(args, 'dssim_weight', 0.0)
+    if not 0.0 <= a <= 1.0:                                            # (NaN fails both comparisons)
+        raise RuntimeError('`--dssim_weight` should be in [0, 1] (got %r)' % (a,))
+
+
+def with_dssim(args, loss_funcs, names):
+    """``--dssim_weight A``: the entries ``names`` of ``loss_funcs`` wrapped as ``WithDSSIM(old, A)``.  With A = 0 (or arguments that
+    never met the flag: ``evaluate``, ``denoise``) the dictionary comes back untouched, object for object, so the plain-L1 fast
+    paths of the interfaces and the captured step are the ones they were."""
+    a = getattr(args, 'dssim_weight', 0.0)
+    if a > 0.0:
+        for name in names:
+            loss_funcs[name] = WithDSSIM(loss_funcs[name], a)
+        print('Image losses %s: (1 - %g) * loss + %g * DSSIM' % (', '.join(names), a, a))
+    return loss_funcs
+
+
 def check_args(args):
     """The argument errors of ``train_kpcn.py:427-441``."""
     check_multi_spp_args(args)
     check_augment_args(args)
+    check_dssim_args(args)
     if args.manif_learn and not args.use_llpm_buf:
         raise RuntimeError('The manifold learning module requires a llpm-specific buffer.')
     if args.manif_learn and not args.manif_loss:

@@ -43,7 +43,7 @@ def init_model(sizes, args, device):
         models = ts.build_models(sizes, args, pnet_out_size, args.use_llpm_buf, 'LBMC')
         model_fn = ts.model_file(args, grid, lr_pnet, pnet_out_size, w_manif)
         optims, ck = ts.restore_and_optimizers(models, args, model_fn, lr_pnet, device)
-        loss_funcs = ts.manifold_loss(args, {'l_recon': ClampedSMAPE(), 'l_test': RelativeMSE()})
+        loss_funcs = ts.tk.with_dssim(args, ts.manifold_loss(args, {'l_recon': ClampedSMAPE(), 'l_test': RelativeMSE()}), ('l_recon',))
         itf = LBMCInterface(models, optims, loss_funcs, args, args.use_llpm_buf, args.manif_learn, w_manif, args.disentangle)
         if ck is not None and args.best_err is not None:
             print('Use the checkpoint best error %.3e' % (args.best_err))

@@ -157,7 +157,7 @@ def init_model(sizes, args, device):
             raise RuntimeError('No such feature combination defined.')
         model_fn = model_file(args, grid, lr_pnet, pnet_out_size, w_manif)
         optims, ck = restore_and_optimizers(models, args, model_fn, lr_pnet, device)
-        loss_funcs = manifold_loss(args, {'l_recon': TonemappedRelativeMSE(), 'l_test': RelativeMSE()})
+        loss_funcs = tk.with_dssim(args, manifold_loss(args, {'l_recon': TonemappedRelativeMSE(), 'l_test': RelativeMSE()}), ('l_recon',))
         itf = SBMCInterface(models, optims, loss_funcs, args, args.visual, args.use_llpm_buf, args.manif_learn, w_manif,
                             args.use_sbmc_buf, args.disentangle)
         if ck is not None and args.best_err is not None:
